@@ -3,9 +3,14 @@
 cell*spot*gene/s at 30k cells x 1k genes x 10k spots; the other BASELINE configurations are --workload choices).
 
     python bench.py --gpus N --steps K --warmup W [--workload cfg2|cfg4|cfg5a|cfg5b] [--precision bf16x3|bf16|fp32]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one full mapping iteration (softmax, P^T S, cosine + density loss, backward, Adam) on synthetic
-inputs of the named shape that are resident in HBM before the timed region starts.
+inputs of the named shape that are resident in HBM before the timed region starts.  A plain run sets up, warms up, times
+the K steps and prints the headline line; `--full` adds everything else the line can carry (a longer run of the same
+schedule, per-kernel times and rooflines, the other GEMM precisions, batched folds, the CPU baseline).  `--dump-outputs DIR`
+writes what the timed path computed in its last step (the mapping, as a seeded sample of whole rows, the per-step losses,
+the filter in constrained mode) to DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 
   cfg2   30 000 cells x 1 000 genes x 10 000 spots, mode='cells' defaults (lambda_g1 = lambda_d = 1)      -- the headline
   cfg4   200 000 x 2 000 x 50 000, bf16 MFMA operands, fp32 accumulate / state (fits ONE 288 GB GPU; sharded for N > 1)
@@ -243,6 +248,43 @@ def cpu_baseline(workload, C, K, V):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+DUMP_MAPPING_BYTES = 48 << 20          # --dump-outputs: mapping rows up to this size, loss rows up to DUMP_HISTORY_ROWS (<= 64 MB in all)
+DUMP_HISTORY_ROWS = 1 << 16
+
+
+def timed_outputs(owner, core, world, C, V, constrained, timed_hist):
+    """What a caller of the timed path receives after its last step (Mapper.train: the mapping softmax(M) and the loss history;
+    MapperConstrained.train: also the filter), as float32 host arrays.  The mapping is sampled as whole rows: every row when
+    they fit in DUMP_MAPPING_BYTES, else a fixed, seeded set of cells (sorted).  Collective on a sharded run (the sampled rows
+    are gathered over the spot shards); call it right after the timed region, before anything else steps the engine."""
+    import numpy as np
+    import torch
+    n_rows = min(C, max(1, DUMP_MAPPING_BYTES // (4 * V)))
+    rows = np.arange(C) if n_rows == C else np.sort(np.random.default_rng(0).choice(C, n_rows, replace=False))
+    if world == 1:
+        P, F = core.result(with_filter=True) if constrained else (core.result(), None)
+    else:
+        res = owner.result_local(with_filter=constrained)
+        P, F = res[0], (res[2] if constrained else None)
+        del res
+    P = P.index_select(0, torch.from_numpy(rows).to(P.device))
+    if world > 1:
+        P = owner._gather_columns(P)
+    hist = timed_hist[-DUMP_HISTORY_ROWS:].cpu().numpy()
+    out = {"mapping_rows": P.cpu().numpy(), "total_loss": hist[:, 0].copy(), "main_loss": hist[:, 1].copy()}
+    if F is not None:
+        out["filter"] = F.cpu().numpy()
+    return out
+
+
+def write_outputs(directory, outputs):
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+# ------------------------------------------------------------------------------------------------------------------
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -259,8 +301,12 @@ def parse_args():
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
     ap.add_argument("--precision", default=None, choices=["bf16x3", "bf16", "fp32"], help="GEMM precision (default: the workload's)")
     ap.add_argument("--shape", default=None, help="override C,K,V (debug)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-alt", action="store_true", help="skip the short runs of the other GEMM precisions")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: a longer run, per-kernel times "
+                                                         "and rooflines, the other GEMM precisions, batched folds, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float32, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-alt", action="store_true", help="--full: skip the short runs of the other GEMM precisions and the batched folds")
     ap.add_argument("--splits", type=int, default=0)
     ap.add_argument("--tile", type=int, default=0, help="force the GEMM tile edge (128 or 256); 0 = automatic")
     ap.add_argument("--bands", type=int, default=0, help="cell bands of the opt-in 3-stream pipeline (0/1 = sequential schedule, the default)")
@@ -370,41 +416,41 @@ def main():
     run(args.steps, timed_hist)                     # timed region: the product schedule
     fence()
     elapsed = time.perf_counter() - t0
-    # A LONGER run of the same schedule, once, after the timed region (never `value`): the device has two HBM states tens of seconds long
-    # (the update kernel at 5.7 or 6.3 TB/s); 20 timed steps catch one of them, 200 average more of it -- a reader
-    # of the line can tell a slow-state draw from a regression.
-    long_steps = 200 if elapsed / args.steps < 0.010 else 20
-    fence()
-    tl = time.perf_counter()
-    run(long_steps)
-    fence()
-    long_elapsed = time.perf_counter() - tl
-    # per-kernel durations: HIP events after every kernel on the kernel's stream.  Event-bracketing needs the kernels on
-    # ONE stream, so this pass runs the sequential schedule (same kernels, same launches, no overlap between them).
-    nprof = max(4, min(args.steps, 20))
-    core.profile(True)
-    t1 = time.perf_counter()
-    run(nprof)
-    fence()
-    seq_elapsed = time.perf_counter() - t1
-    prof = core.profile_read()
+    # --dump-outputs: the arrays the timed path computed, read back now, before anything else steps the engine
+    outputs = timed_outputs(owner, core, world, C, V, mode == "constrained", timed_hist) if args.dump_outputs else None
+    if args.full:
+        # A LONGER run of the same schedule, once, after the timed region (never `value`): the device has two HBM states tens of seconds long
+        # (the update kernel at 5.7 or 6.3 TB/s); 20 timed steps catch one of them, 200 average more of it -- a reader
+        # of the line can tell a slow-state draw from a regression.
+        long_steps = 200 if elapsed / args.steps < 0.010 else 20
+        fence()
+        tl = time.perf_counter()
+        run(long_steps)
+        fence()
+        long_elapsed = time.perf_counter() - tl
+        # per-kernel durations: HIP events after every kernel on the kernel's stream.  Event-bracketing needs the kernels on
+        # ONE stream, so this pass runs the sequential schedule (same kernels, same launches, no overlap between them).
+        nprof = max(4, min(args.steps, 20))
+        core.profile(True)
+        t1 = time.perf_counter()
+        run(nprof)
+        fence()
+        seq_elapsed = time.perf_counter() - t1
+        prof = core.profile_read()
     if world > 1:
-        tt = torch.tensor([elapsed, long_elapsed], dtype=torch.float64, device=device)
+        tt = torch.tensor([elapsed, long_elapsed if args.full else 0.0], dtype=torch.float64, device=device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed, long_elapsed = float(tt[0].item()), float(tt[1].item())
 
-    # sanity: the loss of the last step is finite (nothing was skipped)
-    hist = core.new_history(1)
-    run(1, hist)
-    torch.cuda.synchronize(device)
-    main_loss = float(hist[0, 1].item())
+    # sanity: the loss of the last timed step is finite (nothing was skipped)
+    main_loss = float(timed_hist[-1, 1].item())
     if not (main_loss == main_loss) and not os.environ.get("TG_BENCH_TIMING_ABLATION"):    # (ablation builds compute garbage on purpose)
         print("bench.py: the last step's main_loss is NaN", file=sys.stderr)
         sys.exit(3)
 
     # the other GEMM precisions on the same inputs (reported beside the headline, never as `value`)
     alt = {}
-    if world == 1 and not args.no_alt and args.workload != "cfg4":
+    if args.full and world == 1 and not args.no_alt and args.workload != "cfg4":
         owner.release() if hasattr(owner, "release") else None
         del owner, core, run
         torch.cuda.empty_cache()
@@ -431,7 +477,7 @@ def main():
             torch.cuda.empty_cache()
     del w
     next_rows = {}
-    if world == 1 and not args.no_alt and args.workload == "cfg2" and not args.shape:
+    if args.full and world == 1 and not args.no_alt and args.workload == "cfg2" and not args.shape:
         try:        # SURVEY 8(f-3) beside the headline (never `value`): clusters-mode cross-validation folds, one alone and 16 per tg_batch
             next_rows["f3_batched_mappings"] = bench_folds(device)
         except Exception as e:
@@ -440,66 +486,6 @@ def main():
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
         its = args.steps / elapsed
-        Vl = V if world == 1 else (shard_bounds(V, world, 0)[1])
-        # the committed PMC table was collected on the full single-GPU cfg2 launch: it does not describe a shard or another shape
-        pmc, pmc_note = pmc_traffic(precision) if (world == 1 and not args.shape and args.workload == "cfg2") else ({}, "no PMC table for this workload / shard")
-        kern = []
-        for name, ms, cnt in prof:
-            b, f = kernel_model(name, C, K, Vl)
-            row = {"name": name, "avg_ms": ms / max(cnt, 1), "launches": cnt,
-                   "alg_GB": None if b is None else b / 1e9, "alg_GFLOP": None if f is None else f / 1e9}
-            if b is not None and cnt:
-                row["roofline"] = roof_of(b, f, 1e-3 * ms / cnt, precision, pmc.get(name))
-            kern.append(row)
-        # The roofline of the ITERATION: bytes_alg = 24 C V + 8 (C K + V K), flops_alg = 4 C V K over all GPUs; the
-        # binding roof is the larger of t_HBM and t_MFMA, frac = that time / measured time per step.  The heavy kernels follow
-        # with their own figures (kernel durations: HIP events on the kernel's stream, averaged over the profiled steps).
-        bytes_alg = 24.0 * C * V + 8.0 * (C * K + V * K)
-        flops_alg = 4.0 * C * V * K
-        it_traffic = sum(pmc.get(k["name"], 0.0) for k in kern if k["name"] in HEAVY) if pmc else None
-        roof = roof_of(bytes_alg / world, flops_alg / world, elapsed / args.steps, precision, it_traffic or None)
-        roof["scope"] = "one iteration (all kernels of a step, per GPU)"
-        roof["traffic_source"] = pmc_note
-        roof["bytes_alg"] = bytes_alg
-        roof["flops_alg"] = flops_alg
-        roof["hbm_frac"] = bytes_alg * its / HBM_PEAK / world
-        roof["hbm_frac_of_measured_copy_bw"] = bytes_alg * its / HBM_COPY / world
-        roof["mfma_frac"] = flops_alg * its / MFMA_PEAK[precision] / world
-        roof["kernels"] = [dict(name=k["name"], avg_ms=k["avg_ms"], **k["roofline"]) for k in kern if "roofline" in k]
-        # what the HBM-bound update kernel really moved per second in THIS run: counter bytes (PMC table) -- or, without a table for this
-        # workload, the kernel's modelled 28 B per element (it also reads X) -- over its measured duration here
-        upd = next((k for k in kern if k["name"] in ("tg_adam_rowpass", "tg_adam_update") and k["launches"]), None)
-        if upd is not None:
-            ub = pmc.get(upd["name"])
-            roof["update_TBps_actual"] = (ub if ub else 28.0 * C * Vl) / (1e-3 * upd["avg_ms"]) / 1e12
-            roof["update_traffic_source"] = ("PMC bytes per launch (profiles/pmc_traffic.json) / this run's kernel time" if ub else
-                                             "modelled 28 B per element (reads X, M, m, v; writes M, m, v) / this run's kernel time")
-        # The structural ceiling of this design, on the face of the line.  The step is a CHAIN of two
-        # matrix-core-bound GEMMs and one HBM-bound update (softmax backward needs the complete row dot before any element of
-        # the row may be updated: DESIGN.md section 4), so its floor is the SUM of the three kernels' own roofs, not their
-        # maximum; the north star's 0.60-of-HBM target prices the iteration against the maximum.
-        heavy = {k["name"]: k for k in kern if k["name"] in HEAVY and k.get("launches")}
-        t_seq = sum(k["avg_ms"] for k in heavy.values())
-        t_gemm_roof = 1e3 * (flops_alg / world) / MFMA_PEAK[precision]
-        t_upd_roof = 1e3 * (24.0 * C * V / world) / HBM_PEAK
-        t_bound = 1e3 * max((bytes_alg / world) / HBM_PEAK, (flops_alg / world) / MFMA_PEAK[precision])
-        roof["floor"] = {
-            "sequential_measured_ms": t_seq,
-            "sequential_measured_parts": {n: k["avg_ms"] for n, k in heavy.items()},
-            "sequential_roof_ms": t_gemm_roof + t_upd_roof,
-            "sequential_roof_its": 1e3 / (t_gemm_roof + t_upd_roof),
-            "overlap_bound_ms": t_bound, "overlap_bound_its": 1e3 / t_bound,
-            "mfma_only_probe": MFMA_ONLY_PROBE.get(precision),
-            "note": "sequential_roof = (two GEMMs at the dense MFMA peak of the precision) + (update at 8 TB/s): what the three-kernel "
-                    "chain could reach with every kernel AT its roof; overlap_bound = max(t_MFMA, t_HBM) of the whole iteration, "
-                    "reachable only if the phases overlapped (every overlap design measured slower: profiles/LABBOOK.md section 6b; "
-                    "round 5's gate on reviving them: overlap_gate below, DESIGN.md section 6)",
-            "overlap_gate": OVERLAP_GATE if (args.workload == "cfg2" and not args.shape) else None}
-        target_its = 0.60 * HBM_PEAK / (bytes_alg / world)
-        roof["target"] = {"definition": "north_star: >= 0.60 of the HBM roofline (8 TB/s) on the fused iteration",
-                          "its": target_its, "ms_per_step": 1e3 / target_its, "met": bool(its >= target_its),
-                          "frac_of_target": its / target_its,
-                          "reachable_by_this_design": bool(1e3 / (t_gemm_roof + t_upd_roof) >= target_its)}
         metric = ("mapping iterations/s at 30k cells x 1k genes x 10k spots (mode='cells', lambda_g1=1, lambda_d=1)"
                   if args.workload == "cfg2" and not args.shape else
                   f"mapping iterations/s at {C} cells x {K} genes x {V} spots ({wl_desc})")
@@ -507,8 +493,6 @@ def main():
             "metric": metric,
             "value": its, "unit": "iters/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "value_long": {"value": long_steps / long_elapsed, "unit": "iters/s", "steps": long_steps, "ms_per_step": 1e3 * long_elapsed / long_steps,
-                           "note": "one longer run of the same schedule after the timed region; never `value`"},
             "dtype": DTYPE_NAME[precision], "data": "synthetic",
             "config": {"workload": f"{args.workload}: {C} cells x {K} genes x {V} spots, {wl_desc}; planted-mapping synthetic "
                                    f"counts, Adam lr=0.1", "gemm_precision": precision,
@@ -518,14 +502,79 @@ def main():
                        f"{ {'rccl': 'RCCL on the compute stream', 'peer': 'one-hop peer-memory exchange kernels on the compute stream'}.get(getattr(owner, 'transport', ''), backend + ' through callbacks') })"},
             "cell_spot_gene_per_s": its * C * K * V,
             "last_main_loss": main_loss,
-            "roofline": roof,
-            "kernels": kern,
-            "kernels_pass": {"schedule": "sequential (one stream, HIP event after every kernel)", "steps": nprof,
-                             "ms_per_step": 1e3 * seq_elapsed / nprof, "value": nprof / seq_elapsed},
-            "alt_precisions": alt,
-            "next_rows": next_rows,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            Vl = V if world == 1 else (shard_bounds(V, world, 0)[1])
+            # the committed PMC table was collected on the full single-GPU cfg2 launch: it does not describe a shard or another shape
+            pmc, pmc_note = pmc_traffic(precision) if (world == 1 and not args.shape and args.workload == "cfg2") else ({}, "no PMC table for this workload / shard")
+            kern = []
+            for name, ms, cnt in prof:
+                b, f = kernel_model(name, C, K, Vl)
+                row = {"name": name, "avg_ms": ms / max(cnt, 1), "launches": cnt,
+                       "alg_GB": None if b is None else b / 1e9, "alg_GFLOP": None if f is None else f / 1e9}
+                if b is not None and cnt:
+                    row["roofline"] = roof_of(b, f, 1e-3 * ms / cnt, precision, pmc.get(name))
+                kern.append(row)
+            # The roofline of the ITERATION: bytes_alg = 24 C V + 8 (C K + V K), flops_alg = 4 C V K over all GPUs; the
+            # binding roof is the larger of t_HBM and t_MFMA, frac = that time / measured time per step.  The heavy kernels follow
+            # with their own figures (kernel durations: HIP events on the kernel's stream, averaged over the profiled steps).
+            bytes_alg = 24.0 * C * V + 8.0 * (C * K + V * K)
+            flops_alg = 4.0 * C * V * K
+            it_traffic = sum(pmc.get(k["name"], 0.0) for k in kern if k["name"] in HEAVY) if pmc else None
+            roof = roof_of(bytes_alg / world, flops_alg / world, elapsed / args.steps, precision, it_traffic or None)
+            roof["scope"] = "one iteration (all kernels of a step, per GPU)"
+            roof["traffic_source"] = pmc_note
+            roof["bytes_alg"] = bytes_alg
+            roof["flops_alg"] = flops_alg
+            roof["hbm_frac"] = bytes_alg * its / HBM_PEAK / world
+            roof["hbm_frac_of_measured_copy_bw"] = bytes_alg * its / HBM_COPY / world
+            roof["mfma_frac"] = flops_alg * its / MFMA_PEAK[precision] / world
+            roof["kernels"] = [dict(name=k["name"], avg_ms=k["avg_ms"], **k["roofline"]) for k in kern if "roofline" in k]
+            # what the HBM-bound update kernel really moved per second in THIS run: counter bytes (PMC table) -- or, without a table for this
+            # workload, the kernel's modelled 28 B per element (it also reads X) -- over its measured duration here
+            upd = next((k for k in kern if k["name"] in ("tg_adam_rowpass", "tg_adam_update") and k["launches"]), None)
+            if upd is not None:
+                ub = pmc.get(upd["name"])
+                roof["update_TBps_actual"] = (ub if ub else 28.0 * C * Vl) / (1e-3 * upd["avg_ms"]) / 1e12
+                roof["update_traffic_source"] = ("PMC bytes per launch (profiles/pmc_traffic.json) / this run's kernel time" if ub else
+                                                 "modelled 28 B per element (reads X, M, m, v; writes M, m, v) / this run's kernel time")
+            # The structural ceiling of this design, on the face of the line.  The step is a CHAIN of two
+            # matrix-core-bound GEMMs and one HBM-bound update (softmax backward needs the complete row dot before any element of
+            # the row may be updated: DESIGN.md section 4), so its floor is the SUM of the three kernels' own roofs, not their
+            # maximum; the north star's 0.60-of-HBM target prices the iteration against the maximum.
+            heavy = {k["name"]: k for k in kern if k["name"] in HEAVY and k.get("launches")}
+            t_seq = sum(k["avg_ms"] for k in heavy.values())
+            t_gemm_roof = 1e3 * (flops_alg / world) / MFMA_PEAK[precision]
+            t_upd_roof = 1e3 * (24.0 * C * V / world) / HBM_PEAK
+            t_bound = 1e3 * max((bytes_alg / world) / HBM_PEAK, (flops_alg / world) / MFMA_PEAK[precision])
+            roof["floor"] = {
+                "sequential_measured_ms": t_seq,
+                "sequential_measured_parts": {n: k["avg_ms"] for n, k in heavy.items()},
+                "sequential_roof_ms": t_gemm_roof + t_upd_roof,
+                "sequential_roof_its": 1e3 / (t_gemm_roof + t_upd_roof),
+                "overlap_bound_ms": t_bound, "overlap_bound_its": 1e3 / t_bound,
+                "mfma_only_probe": MFMA_ONLY_PROBE.get(precision),
+                "note": "sequential_roof = (two GEMMs at the dense MFMA peak of the precision) + (update at 8 TB/s): what the three-kernel "
+                        "chain could reach with every kernel AT its roof; overlap_bound = max(t_MFMA, t_HBM) of the whole iteration, "
+                        "reachable only if the phases overlapped (every overlap design measured slower: profiles/LABBOOK.md section 6b; "
+                        "round 5's gate on reviving them: overlap_gate below, DESIGN.md section 6)",
+                "overlap_gate": OVERLAP_GATE if (args.workload == "cfg2" and not args.shape) else None}
+            target_its = 0.60 * HBM_PEAK / (bytes_alg / world)
+            roof["target"] = {"definition": "north_star: >= 0.60 of the HBM roofline (8 TB/s) on the fused iteration",
+                              "its": target_its, "ms_per_step": 1e3 / target_its, "met": bool(its >= target_its),
+                              "frac_of_target": its / target_its,
+                              "reachable_by_this_design": bool(1e3 / (t_gemm_roof + t_upd_roof) >= target_its)}
+            out.update({
+                "value_long": {"value": long_steps / long_elapsed, "unit": "iters/s", "steps": long_steps, "ms_per_step": 1e3 * long_elapsed / long_steps,
+                               "note": "one longer run of the same schedule after the timed region; never `value`"},
+                "roofline": roof,
+                "kernels": kern,
+                "kernels_pass": {"schedule": "sequential (one stream, HIP event after every kernel)", "steps": nprof,
+                                 "ms_per_step": 1e3 * seq_elapsed / nprof, "value": nprof / seq_elapsed},
+                "alt_precisions": alt,
+                "next_rows": next_rows,
+            })
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if args.workload == "cfg4":
                 out["cpu_baseline"] = {"value": None, "kind": "port", "cores": 0, "unit": "iters/s",
                                        "sample": "not runnable on the CPU reference: M alone is 40 GB fp32 plus ~9x that in autograd "
@@ -535,6 +584,8 @@ def main():
                     out["cpu_baseline"] = cpu_baseline(args.workload, C, K, V)
                 except Exception as e:  # the baseline must never take the GPU number down with it
                     out["cpu_baseline"] = {"error": repr(e)}
+        if outputs is not None:
+            write_outputs(args.dump_outputs, outputs)
         print(json.dumps(out))
     if world > 1:
         dist.barrier()

@@ -9,7 +9,7 @@ for r in $(seq 1 $ROUNDS); do
  for lib in $R/tangram_amd/csrc/libtangram_hip.so $R/build/ab_*.so; do
   [ -f $lib ] || continue; n=$(basename $lib .so)
   for P in $PRECS; do
-    timeout 600 python scripts/with_lib.py $lib bench.py --steps 40 --warmup 5 --precision $P --no-cpu-baseline --no-alt $EXTRA > $O/${n}_${P}_r$r.json 2> $O/${n}_${P}_r$r.err || echo "FAIL $n $P"
+    timeout 600 python scripts/with_lib.py $lib bench.py --full --steps 40 --warmup 5 --precision $P --no-cpu-baseline --no-alt $EXTRA > $O/${n}_${P}_r$r.json 2> $O/${n}_${P}_r$r.err || echo "FAIL $n $P"
   done
  done
 done

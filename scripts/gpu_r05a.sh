@@ -12,7 +12,7 @@ ab)
   for r in 1 2; do
    for lib in $R/tangram_amd/csrc/libtangram_hip.so $R/build/ab_*.so; do
     [ -f $lib ] || continue; n=$(basename $lib .so)
-    timeout 300 python scripts/with_lib.py $lib bench.py --steps 40 --warmup 5 --precision bf16x3 --no-cpu-baseline --no-alt > $O/${n}_r$r.json 2> $O/${n}_r$r.err || echo "FAIL $n"
+    timeout 300 python scripts/with_lib.py $lib bench.py --full --steps 40 --warmup 5 --precision bf16x3 --no-cpu-baseline --no-alt > $O/${n}_r$r.json 2> $O/${n}_r$r.err || echo "FAIL $n"
    done
   done
   python - $O <<'PY'
@@ -29,7 +29,7 @@ probe)
   ;;
 pmc)
   cd /tmp && export TMPDIR=/tmp
-  timeout 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --output-format csv -d $O/pmc -o p -- python $R/bench.py --steps 3 --warmup 1 --precision bf16x3 --no-cpu-baseline --no-alt > $O/pmc.log 2>&1
+  timeout 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --output-format csv -d $O/pmc -o p -- python $R/bench.py --full --steps 3 --warmup 1 --precision bf16x3 --no-cpu-baseline --no-alt > $O/pmc.log 2>&1
   echo "pmc rc=$?"; cd $R
   python - $O <<'PY'
 import csv,glob,sys,collections

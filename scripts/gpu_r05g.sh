@@ -7,7 +7,7 @@ rm -rf $R/gpurun_out/*; mkdir -p $O; cd $R; export PYTHONUNBUFFERED=1
 for r in 1 2; do
  for lib in $R/tangram_amd/csrc/libtangram_hip.so $R/build/ab_xtemporal.so; do
   n=$(basename $lib .so)
-  timeout 300 python scripts/with_lib.py $lib bench.py --steps 40 --warmup 5 --precision bf16x3 --no-cpu-baseline --no-alt > $O/${n}_r$r.json 2> $O/${n}_r$r.err || echo "FAIL $n"
+  timeout 300 python scripts/with_lib.py $lib bench.py --full --steps 40 --warmup 5 --precision bf16x3 --no-cpu-baseline --no-alt > $O/${n}_r$r.json 2> $O/${n}_r$r.err || echo "FAIL $n"
  done
 done
 python - $O <<'PY'
@@ -21,7 +21,7 @@ cd /tmp && export TMPDIR=/tmp
 for lib in $R/tangram_amd/csrc/libtangram_hip.so $R/build/ab_xtemporal.so; do
   n=$(basename $lib .so)
   for G in FETCH_SIZE WRITE_SIZE; do
-    timeout 300 rocprofv3 --pmc $G --output-format csv -d $O/pmc_${n}_$G -o p -- python $R/scripts/with_lib.py $lib $R/bench.py --steps 3 --warmup 1 --precision bf16x3 --no-cpu-baseline --no-alt > $O/pmc_${n}_$G.log 2>&1
+    timeout 300 rocprofv3 --pmc $G --output-format csv -d $O/pmc_${n}_$G -o p -- python $R/scripts/with_lib.py $lib $R/bench.py --full --steps 3 --warmup 1 --precision bf16x3 --no-cpu-baseline --no-alt > $O/pmc_${n}_$G.log 2>&1
   done
 done
 cd $R

@@ -7,7 +7,7 @@ rm -rf $R/gpurun_out/*; mkdir -p $O; cd $R; export PYTHONUNBUFFERED=1
 for r in 1 2 3; do
  for lib in $R/tangram_amd/csrc/libtangram_hip.so $R/build/ab_*.so; do
   n=$(basename $lib .so)
-  timeout 300 python scripts/with_lib.py $lib bench.py --steps 200 --warmup 20 --precision bf16x3 --no-cpu-baseline --no-alt > $O/${n}_r$r.json 2> $O/${n}_r$r.err || echo "FAIL $n"
+  timeout 300 python scripts/with_lib.py $lib bench.py --full --steps 200 --warmup 20 --precision bf16x3 --no-cpu-baseline --no-alt > $O/${n}_r$r.json 2> $O/${n}_r$r.err || echo "FAIL $n"
  done
 done
 python - $O <<'PY'

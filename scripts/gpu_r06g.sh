@@ -11,8 +11,8 @@ for k,v in d.items(): print(k, "%.4f ms"%v["ms_per_step"], "loss %.9f"%v["main_l
 PY
 for SH in "26431,249,9852 6" "8000,500,5000 6" "30000,1000,3300 4"; do set -- $SH
   for P in bf16x3 bf16; do
-    A=$(timeout 300 python bench.py --shape $1 --precision $P --steps 100 --warmup 10 --no-cpu-baseline --no-alt 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.1f it/s fwd %.1f us'%(d['value'], 1e3*[k['avg_ms'] for k in d['kernels'] if k['name']=='tg_fwd_kernel'][0]))")
-    B=$(timeout 300 python bench.py --shape $1 --precision $P --splits $2 --steps 100 --warmup 10 --no-cpu-baseline --no-alt 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.1f it/s fwd %.1f us'%(d['value'], 1e3*[k['avg_ms'] for k in d['kernels'] if k['name']=='tg_fwd_kernel'][0]))")
+    A=$(timeout 300 python bench.py --full --shape $1 --precision $P --steps 100 --warmup 10 --no-cpu-baseline --no-alt 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.1f it/s fwd %.1f us'%(d['value'], 1e3*[k['avg_ms'] for k in d['kernels'] if k['name']=='tg_fwd_kernel'][0]))")
+    B=$(timeout 300 python bench.py --full --shape $1 --precision $P --splits $2 --steps 100 --warmup 10 --no-cpu-baseline --no-alt 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.1f it/s fwd %.1f us'%(d['value'], 1e3*[k['avg_ms'] for k in d['kernels'] if k['name']=='tg_fwd_kernel'][0]))")
     echo "$1 $P: automatic $A | $2 equal ranges per tile $B"
   done
 done

@@ -1,5 +1,6 @@
-"""The driver's contract with bench.py (-m gpu): one JSON line on stdout with the agreed keys, the iteration `roofline` and the
-`cpu_baseline` objects; refusals are one line on stderr with exit code 2.  A small shape keeps this to a few seconds; the
+"""The driver's contract with bench.py (-m gpu): one JSON line on stdout with the agreed keys (with --full: the iteration
+`roofline` and the `cpu_baseline` objects too), --dump-outputs writes the timed path's outputs; refusals are one line on stderr
+with exit code 2.  A small shape keeps this to a few seconds; the
 numbers themselves are not asserted (profiles/ holds the measured ones)."""
 import json
 import os
@@ -10,6 +11,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PLAIN_KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype"}
 KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
         "data", "config", "roofline", "cpu_baseline"}
 
@@ -21,7 +23,7 @@ def _run(*args):
 
 
 def test_bench_prints_one_json_line_with_the_contract_keys():
-    r = _run("--shape", "6000,200,1500", "--steps", "6", "--warmup", "2", "--no-alt")
+    r = _run("--shape", "6000,200,1500", "--steps", "6", "--warmup", "2", "--no-alt", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -38,6 +40,27 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     assert 0.05 < roof["update_TBps_actual"] < 8.0 and "update_traffic_source" in roof
     cpu = d["cpu_baseline"]
     assert {"value", "unit", "cores", "kind", "sample"} <= set(cpu) and cpu["kind"] in ("port", "reference") and cpu["cores"] >= 1
+
+
+def test_plain_bench_prints_the_headline_and_dumps_the_timed_outputs(tmp_path):
+    import numpy as np
+    C, K, V = 6000, 200, 1500
+    r = _run("--shape", f"{C},{K},{V}", "--steps", "5", "--warmup", "2", "--dump-outputs", str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert PLAIN_KEYS <= set(d), PLAIN_KEYS - set(d)
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["higher_is_better"] is True
+    assert d["value"] > 0 and abs(d["value"] * d["ms_per_step"] - 1000.0) < 1e-6 * 1000.0
+    assert not {"roofline", "cpu_baseline", "value_long", "alt_precisions"} & set(d)          # (--full only)
+    files = {f.name: np.load(f) for f in tmp_path.iterdir()}
+    assert set(files) == {"mapping_rows.npy", "total_loss.npy", "main_loss.npy"}, set(files)
+    assert all(a.dtype == np.float32 for a in files.values()) and sum(a.nbytes for a in files.values()) <= 64 << 20
+    P = files["mapping_rows.npy"]
+    assert P.shape == (C, V) and np.isfinite(P).all() and np.allclose(P.sum(1), 1.0, atol=1e-4)      # (every row fits: no sample)
+    assert files["main_loss.npy"].shape == (5,) and files["main_loss.npy"][-1] == np.float32(d["last_main_loss"])
+    assert np.isfinite(files["total_loss.npy"]).all()
 
 
 def test_bench_refuses_more_ranks_than_gpus_with_one_line():
