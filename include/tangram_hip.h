@@ -168,7 +168,8 @@ int tg_comm_peer_create(int world, int rank, size_t capacity_floats, int same_pr
  * per-gene statistics are pushed and polled inside tg_gene_reduce; the update kernel sums the backward GEMM's row-dot partials of its
  * row itself, pushes them, polls the peers' and goes on (its first loads already in flight); the row pairs are pushed from the update
  * kernel's tail and polled at the head of tg_merge_stats: 7 launches per step instead of 11, every sum in the same order as on the other
- * transports (bit-identical results).  Runs with spatial terms keep the exchange kernels.  colocated: how many ranks of this communicator
+ * transports (bit-identical results).  Runs with spatial terms, and runs of more than 6128 padded gene columns (K > 6015 on 128 tiles,
+ * K > 5887 on 256: the loss is finalised without the update kernel's history workgroup), keep the exchange kernels.  colocated: how many ranks of this communicator
  * run on THIS rank's device (1 in deployment; the one-GPU tests pass the world size: kernels that wait for their peers then leave room
  * for the peers' kernels). */
 int tg_comm_peer_create_stepped(int world, int rank, size_t capacity_floats, size_t step_floats, int colocated, int same_process,

@@ -69,7 +69,16 @@ ROWPASS_MAX_SPOTS = 16384          # TG_ROWPASS_MAX_V (tg_capi.hip): rows the si
 BATCH_MAX_ELEMENTS = 1 << 25       # cells x spots above which ONE mapping fills the GPU: batching then LOSES (measured, B = 2 - 4 vs one
                                    # after the other: 4 200 x 1 100: 1.4 - 1.75x, 8 000 x 3 000: 1.05 - 1.13x, 12 000 x 5 000: 0.96 - 0.98x,
                                    # 26 431 x 9 852: 0.83 - 0.85x; profiles/r03/run15_batch_sizes)
-EMIT_MAX_GENE_COLS = 6128          # (2 Kp + 32) floats of dynamic LDS <= 48 KB in tg_dghat_emit<SELF>
+EMIT_MAX_GENE_COLS = 6128          # (2 Kp + 32) floats of dynamic LDS <= 48 KB in tg_dghat_emit<SELF>: Kp = rup(K + 1, tile) <= 6128
+
+
+def _gene_cols(e):
+    """Kp of the handle's layout: its K + 1 operand columns rounded up to the tile (no cell-type columns: no spatial terms here)."""
+    if e.K + 1 + 255 <= EMIT_MAX_GENE_COLS:                 # fits whatever the tile (128 or 256)
+        return e.K + 1
+    geo = (ct.c_int * 8)()
+    _capi.check(e._lib.tg_debug_layout(ct.byref(e.cfg), geo))
+    return -(-(e.K + 1) // geo[0]) * geo[0]
 
 
 def _batch_key(m):
@@ -83,7 +92,7 @@ def _batch_key(m):
         return None
     if e.C * e.V > BATCH_MAX_ELEMENTS:
         return None
-    if e.V > ROWPASS_MAX_SPOTS or e.K + 1 + 256 > EMIT_MAX_GENE_COLS or c.pipeline_bands > 1:
+    if e.V > ROWPASS_MAX_SPOTS or c.pipeline_bands > 1 or _gene_cols(e) > EMIT_MAX_GENE_COLS:
         return None
     stream = e._torch_stream.cuda_stream if e._torch_stream is not None else 0
     # (effective_precision: folds built with s_exact="auto" whose S differs in bf16-exactness run different GEMM kernels)

@@ -1346,7 +1346,8 @@ extern "C" int tg_batch_create(tg_mapper* const* mappers, int n, void* scratch_d
         if (m->step != m0->step) return tg_fail(TG_ERR_INVALID, "all mappers of a batch must be at the same step");
         if (m->cfg.mode != m0->cfg.mode) return tg_fail(TG_ERR_INVALID, "a batch holds handles of ONE class (Mapper or MapperConstrained)");
         if (m->comm || A.Vtot != A.V || A.bands > 1 || !tg_emit_self_ok(m) || A.V > TG_ROWPASS_MAX_V)
-            return tg_fail(TG_ERR_UNSUPPORTED, "mapper %d uses spatial terms, spot shards, the band pipeline or rows longer than %d spots", i, TG_ROWPASS_MAX_V);
+            return tg_fail(TG_ERR_UNSUPPORTED, "mapper %d uses spatial terms, spot shards, the band pipeline, rows longer than %d spots or more genes "
+                           "than the emitter holds (%d padded gene columns, at most 6128: K <= 6015 on 128 tiles, 5887 on 256)", i, TG_ROWPASS_MAX_V, A.Kp);
         if (m->cfg.beta1 != m0->cfg.beta1 || m->cfg.beta2 != m0->cfg.beta2) return tg_fail(TG_ERR_INVALID, "Adam betas differ inside the batch");
         for (int j = 0; j < i; ++j) if (mappers[j] == m) return tg_fail(TG_ERR_INVALID, "mapper %d appears twice in the batch", i);
     }
@@ -1888,10 +1889,12 @@ extern "C" int tg_mapper_attach_comm(tg_mapper* m, tg_comm* comm) {
                        comm->rank, comm->world, comm->rank * L.Vmaxl, L.nranks, m->cfg.spot_offset);
     m->comm = comm;
     // Round 6: on the peer transport with a step area the three exchanges of a step happen inside its kernels (tg_one_step_sharded).
+    // Only where the emitter derives its own coefficients (tg_emit_self_ok: Kp <= 6128 genes): the E1 tail of the step is pushed by the
+    // update kernel's history workgroup, which a step through tg_loss_finalize does not have.  (Reads m->comm: after it is set.)
     // TG_PEER_FUSED=0 (environment) keeps the exchange kernels of round 5 (A / B measurements).
     {
         const char* e = getenv("TG_PEER_FUSED");
-        m->fused = comm->peer_mode && comm->step_cap >= L.step_floats && L.step_floats > 0 && !L.sp_shard && !(e && *e == '0');
+        m->fused = comm->peer_mode && comm->step_cap >= L.step_floats && L.step_floats > 0 && !L.sp_shard && !(e && *e == '0') && tg_emit_self_ok(m);
     }
     if (comm->peer_mode) {                                       // every rank's mailbox as mapped here: the kernels' table (TgPeerLink::box)
         static_assert(TG_PEER_MAX * sizeof(void*) <= 256, "the mailbox table has a 256-byte block");

@@ -17,7 +17,8 @@ exchanges -- is issued by the C library inside `tg_mapper_step` (include/tangram
     mailbox, polled in the own one, summed in rank order): the latency of a kernel launch, not of a 2 (N - 1)-hop ring.
     Round 6: with a STEP AREA in the mailbox (tg_comm_peer_create_stepped) a step launches no exchange kernel at all -- the per-gene statistics
     are pushed and polled inside tg_gene_reduce, the row sums inside the update kernel (the row stays in registers across the exchange),
-    the row pairs are pushed from the update kernel's tail and polled at the head of the merge.  OPT-IN (`transport="peer_checked"`,
+    the row pairs are pushed from the update kernel's tail and polled at the head of the merge (up to 6128 padded gene columns,
+    K <= 6015 on 128 tiles: wider runs, and runs with spatial terms, keep the exchange kernels).  OPT-IN (`transport="peer_checked"`,
     or TG_SHARD_TRANSPORT=peer_checked in the environment): set-up + a self-test against the group's own all-reduce / all-gather on
     this very topology, all ranks agreeing on the verdict; any failure (mailbox allocation, hipIpc mapping, a wrong or late result)
     falls back to "rccl", logged.  `transport="auto"` (the default) is RCCL on an nccl group: the peer transport has never crossed

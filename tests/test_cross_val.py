@@ -38,13 +38,13 @@ def test_fold_generator_matches_sklearn(K):
         list(tg.cv_data_gen(ad_sc, ad_sp))
 
 
-def _sequential_reference_procedure(ad_sc, ad_sp, folds, mode, epochs, **kw):
+def _sequential_reference_procedure(ad_sc, ad_sp, folds, mode, epochs, device="cpu", **kw):
     """utils.py:566-640 with this package's map_cells_to_space: one fold after the other, projection and scores on the host."""
     import tangram_amd as tg
-    src = tg.adata_to_cluster_expression(ad_sc, kw["cluster_label"], True, device="cpu") if mode == "clusters" else ad_sc
+    src = tg.adata_to_cluster_expression(ad_sc, kw["cluster_label"], True, device=device) if mode == "clusters" else ad_sc
     tests, trains, preds = [], [], []
     for train_genes, test_genes in folds:
-        ad_map = tg.map_cells_to_space(ad_sc, ad_sp, cv_train_genes=train_genes, mode=mode, device="cpu", num_epochs=epochs,
+        ad_map = tg.map_cells_to_space(ad_sc, ad_sp, cv_train_genes=train_genes, mode=mode, device=device, num_epochs=epochs,
                                        verbose=False, gemm_precision="fp32", **kw)
         pred = ad_map.X.T.astype(np.float64) @ np.asarray(src[:, test_genes].X, dtype=np.float64)
         g = np.asarray(ad_sp[:, test_genes].X, dtype=np.float64)

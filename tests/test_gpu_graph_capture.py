@@ -38,8 +38,9 @@ def _bits(t):
     return t.detach().cpu().numpy().view(np.uint32)
 
 
-@pytest.mark.parametrize("shape,mode", [((600, 80, 300), "cells"), ((18, 120, 2000), "clusters"), ((300, 60, 200), "constrained")],
-                         ids=["cells", "clusters_sc_kernels", "constrained"])
+@pytest.mark.parametrize("shape,mode", [((600, 80, 300), "cells"), ((18, 120, 2000), "clusters"), ((300, 60, 200), "constrained"),
+                                        ((600, 6200, 300), "cells"), ((300, 6200, 200), "constrained")],
+                         ids=["cells", "clusters_sc_kernels", "constrained", "cells_all_genes", "constrained_all_genes"])
 def test_mapper_step_captured_into_a_graph_replays_bit_identically(shape, mode):
     import torch
     from oracle import tangram_oracle as orc

@@ -71,12 +71,29 @@ def test_peer_transport_over_hip_ipc_equals_the_callback_transport(tmp_path, wor
     collectives (gloo here), all ranks agreeing on the verdict, before the transport is trusted with the run.
     (Ranks as threads of one process cannot test the peer kernels reliably: a rank's exchange kernel waits for its peers' kernels, and
     two streams of one process may share a hardware queue -- measured: the first such case timed out, profiles/r05/run2_peer.)"""
+    _peer_vs_callbacks(tmp_path, world, constrained, transport)
+
+
+# All-genes widths around the self-emit bound (Kp <= 6128 padded gene columns: K <= 6015 on 128 tiles, 5887 on 256): up to it the peer
+# step runs its exchanges inside the kernels, past it (tg_loss_finalize, no history workgroup) it keeps the exchange kernels.
+WIDE_PEER = [((2600, 6015, 1300, 3), 2, False), ((2600, 6016, 1300, 3), 2, False), ((2600, 6200, 1300, 3), 3, True),
+             ((4200, 5888, 1500, 3), 2, False)]
+
+
+@pytest.mark.parametrize("shape,world,constrained", WIDE_PEER, ids=["k6015_fused_edge", "k6016", "k6200_w3_constrained", "k5888_tile256"])
+def test_peer_transport_at_all_genes_widths_equals_the_callback_transport(tmp_path, shape, world, constrained):
+    """The same bit-for-bit comparison at gene counts on both sides of the bound: a fused step whose E1 tail nobody pushes would time out
+    and NaN-poison the history instead."""
+    _peer_vs_callbacks(tmp_path, world, constrained, "peer", shape)
+
+
+def _peer_vs_callbacks(tmp_path, world, constrained, transport, shape=None):
     import socket
     import torch.multiprocessing as mp
     from tangram_amd.sharded import make_sharded
     from tests.local_comm import run_ranks
-    data, M0, kw, lam = _peer_problem(constrained)
-    n = PEER_SHAPE[3]
+    data, M0, kw, lam = _peer_problem(constrained, shape)
+    n = (shape or PEER_SHAPE)[3]
 
     def rank_fn(comm):
         sh = make_sharded(data["S"], data["G"], M0, d=data["d"], device=DEV, precision="bf16x3", lambdas=lam, comm=comm, transport="callbacks", **kw)
@@ -89,9 +106,10 @@ def test_peer_transport_over_hip_ipc_equals_the_callback_transport(tmp_path, wor
     ref = run_ranks(world, rank_fn)
     torch.cuda.synchronize()
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    mp.spawn(_peer_worker, args=(world, port, str(tmp_path), constrained, transport), nprocs=world, join=True)
+    mp.spawn(_peer_worker, args=(world, port, str(tmp_path), constrained, transport, shape), nprocs=world, join=True)
     for r in range(world):
         z = np.load(tmp_path / f"peer_{r}.npz")
+        assert np.isfinite(z["hist"][:, :4]).all(), f"rank {r}: history {z['hist'][:, :4]}"
         for k in ("hist", "M", "P"):
             bad = np.argwhere(~((z[k] == ref[r][k]) | (np.isnan(z[k]) & np.isnan(ref[r][k]))))
             np.testing.assert_array_equal(z[k], ref[r][k], err_msg=f"rank {r}: {k}; first mismatches at (row, column) {bad[:8].tolist()}")
