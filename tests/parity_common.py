@@ -203,3 +203,191 @@ def small_cluster_case(device, C, K, V, constrained, lambda_g2, seed, precision=
         P = e.result()
     assert np.abs(P.cpu().numpy() - Po).max() <= tol["P"], (C, K, V)
     return e
+
+
+# ---- the update kernels at every row length on the GEMM path (tests/test_update_row_lengths.py on the emulator,
+# tests/test_gpu_update_row_lengths.py on the GPU) ------------------------------------------------------------------------------
+# Bounds of update_row_case, calibrated on the emulator and on MI355X (largest measured values: the two test modules' docstrings).
+#   grad: per row, max|g - dM| / max|dM_row| of the first-step gradient (bf16: the 2-norm, ROW_GRAD_NORM); and the last four
+#         columns of every row against the largest |dM| of those columns
+#   P:    element-wise max|P - Po| / Po after n epochs
+#   den:  element-wise relative error of Adam's denominator sqrt(v) / sqrt(1 - beta2^t) + eps after n epochs (the second moment as
+#         the update uses it: an element whose gradient crosses zero has no relative precision in v itself)
+#   F:    constrained mode, the filter logits, |F - Fo| / max(1, |Fo|), and the filter's denominator like `den`
+ROW_TOL = {
+    "fp32":   dict(grad=5e-5, P=5e-5, den=5e-5),
+    "bf16x3": dict(grad=5e-5, P=5e-5, den=5e-5),
+    "bf16":   dict(grad=1e-2, P=1e-2, den=1e-2),
+}
+# Norm of the per-row gradient check.  Plain bf16 rounds S, dGhat and X to 8 mantissa bits: where a row's largest P meets a dP close
+# to r_c, single elements are off by more than 1e-2 (1.4e-2 measured, bit-identical on the emulator and MI355X, at the row's
+# largest |dM|), so bf16 rows are held in the 2-norm -- the norm of the existing bf16 gradient bound (relative Frobenius 1e-2,
+# tests/test_gpu_production_tiles.py), taken per row
+ROW_GRAD_NORM = {"fp32": np.inf, "bf16x3": np.inf, "bf16": 2}
+# Adam's eps of these runs as a fraction of the largest first-step |dM| (see update_row_case); plain bf16 takes a larger one, because
+# its gradient carries ~1e-2 of round-off and the denominator of an element whose gradient is near zero is eps
+ROW_EPS_FRACTION = {"fp32": 0.05, "bf16x3": 0.05, "bf16": 0.2}
+
+
+def update_instantiation(C, V, precision, variant):
+    """The update kernel a single-GPU, more-than-32-cell handle launches (tg_launch_update / tg_launch_rowpass in tg_capi.hip):
+    (kernel, FULL, X16, NQ, NT, STREAM); NQ is None for tg_adam_update."""
+    full, x16 = variant != "plain", precision == "bf16"
+    if V > 16384:                                       # backward with the row-dot epilogue, tg_rowsum_parts, tg_adam_update
+        return ("tg_adam_update", full, x16, None, 1024 if C <= 64 else 256, True)
+    if V > 4096:
+        nq = (V + 2047) // 2048
+        return ("tg_adam_rowpass", full, x16, nq if nq <= 6 else 8, 512, True)
+    nq = (V + 1023) // 1024
+    vp = -(-V // 64) * 64
+    stream = C * vp * (12 + (2 if x16 else 4)) > (192 << 20)      # tg_mapper::stream_once
+    return ("tg_adam_rowpass", full, x16, 1 if nq <= 1 else (2 if nq <= 2 else 4), 256, stream)
+
+
+def _oracle_adam_step(o, eps, lr):
+    """OracleMapper(.Constrained).step with Adam's eps set (the oracle's own step uses torch's default 1e-8)."""
+    from oracle import tangram_oracle as orc
+    res = o.loss_and_grad()
+    o.t += 1
+    if len(res) == 3:
+        terms, dM, dF = res
+        orc.adam_update(o.M, dM, o.mM, o.vM, o.t, lr, eps=eps)
+        orc.adam_update(o.F, dF, o.mF, o.vF, o.t, lr, eps=eps)
+    else:
+        terms, dM = res
+        orc.adam_update(o.M, dM, o.m, o.v, o.t, lr, eps=eps)
+    return terms, dM
+
+
+def row_rel_err(got, ref, order=np.inf):
+    """Per row: |got - ref| / |ref_row| in the max norm (order=inf) or the 2-norm (order=2)."""
+    scale = np.linalg.norm(ref, ord=order, axis=1)
+    return np.linalg.norm(got - ref, ord=order, axis=1) / np.where(scale > 0, scale, 1.0)
+
+
+def update_row_case(device, C, K, V, variant, precision, tile=0, expect_tile=128, n=3, seed=0):
+    """One problem of C > 32 cells on the GEMM path against the fp64 oracle, n epochs; returns the measured errors.
+
+    variant: "plain" (FULL off), "regularised" (lambda_r, lambda_l1, lambda_l2 on) or "constrained" (filter gate + lambda_r).
+    The regularisers are scaled to the plain gradient of the problem so that each term moves dM visibly without drowning the
+    rest.  Adam's eps is ROW_EPS_FRACTION[precision] of the largest first-step |dM|: with torch's 1e-8 the first step is lr * sign(g)
+    wherever |g| >> 1e-8, and the few elements whose gradient crosses zero within the round-off of the GEMM precision then
+    decide an element-wise comparison of P (measured: 5e-4 relative in bf16x3, 0.2 in bf16 at eps 1e-8).  The kernel's
+    arithmetic is the same for any eps."""
+    import ctypes as ct
+    from tangram_amd.engine import HipMapperEngine
+    from tangram_amd import _capi
+    from oracle import tangram_oracle as orc
+    lr = 0.1
+    kind = update_instantiation(C, V, precision, variant)
+    data = orc.make_synthetic(C, K, V, seed=seed)
+    lam = dict(lambda_g1=1.0, lambda_d=1.0, lambda_g2=0.5)
+    if variant == "constrained":
+        M0, F0 = orc.reference_init_MF_constrained(C, V, seed + 1)
+    else:
+        M0, F0 = orc.reference_init_M(C, V, seed + 1), None
+    if variant != "plain":                # each regulariser at a fraction of the typical |dM| of the plain problem
+        _, g0 = orc.OracleMapper(data["S"], data["G"], d=data["d"], M0=M0, dtype=np.float64, **lam).loss_and_grad()
+        P0 = orc.softmax_rows(M0.astype(np.float64))
+        logP = np.log(P0)
+        ent = np.median(np.abs(P0 * (logP - (P0 * logP).sum(axis=1, keepdims=True))))
+        gmed = float(np.median(np.abs(g0)))
+        lam["lambda_r"] = float(np.float32(0.3 * gmed / ent))
+        if variant == "regularised":
+            lam["lambda_l1"] = float(np.float32(0.2 * gmed))
+            lam["lambda_l2"] = float(np.float32(0.1 * gmed))
+    if variant == "constrained":
+        lam.update(lambda_count=1.0, lambda_f_reg=1.0)
+        tc = 0.4 * C
+        o = orc.OracleMapperConstrained(data["S"], data["G"], data["d"], M0=M0, F0=F0, target_count=tc, dtype=np.float64, **lam)
+        kw = dict(F0=F0, mode="constrained", target_count=tc)
+    else:
+        o = orc.OracleMapper(data["S"], data["G"], d=data["d"], M0=M0, dtype=np.float64, **lam)
+        kw = {}
+    dM = o.loss_and_grad()[1]
+    eps = float(np.float32(ROW_EPS_FRACTION[precision] * np.abs(dM).max()))
+    e = HipMapperEngine(data["S"], data["G"], M0, d=data["d"], device=device, precision=precision, lambdas=lam, tile_size=tile,
+                        eps=eps, **kw)
+    tol = ROW_TOL[precision]
+    out = dict(kind=kind, eps=eps)
+    # ---- schedule: the GEMM path (not the clusters-mode kernels), the tile, one cell band
+    geo = (ct.c_int * 8)()
+    assert e._lib.tg_debug_layout(ct.byref(e.cfg), geo) == 0
+    assert (geo[7], geo[0], geo[6]) == (0, expect_tile, 1), f"smallc / tile / bands = {geo[7]}, {geo[0]}, {geo[6]}"
+    M, m1, m2, _ = e.logits()
+    pitch = M.shape[1]
+    pad0 = [x[:, V:].cpu().numpy().copy() for x in (M, m1, m2)]
+    if variant == "constrained":
+        fs = e.filter_state()
+        fpad0 = fs[:, C:].cpu().numpy().copy()
+    hist = e.new_history(n)
+    e.profile(True)
+    e.step(1, lr, hist, 0)
+    names = [k for k, _, _ in e.profile_read()]
+    e.profile(False)
+    if kind[0] == "tg_adam_rowpass":
+        assert "tg_adam_rowpass" in names and "tg_adam_update" not in names and "tg_rowsum_parts" not in names, names
+    else:
+        assert "tg_rowsum_parts" in names and "tg_adam_update" in names and "tg_adam_rowpass" not in names, names
+    # ---- first-step gradient from Adam's first moment: exp_avg = (1 - beta1) * g after one step
+    terms, dM1 = _oracle_adam_step(o, eps, lr)
+    assert np.array_equal(dM1, dM)
+    hist_o = {k: [terms.get(k, np.nan)] for k in terms}
+    g = m1[:, :V].cpu().numpy().astype(np.float64) / (1.0 - 0.9)
+    err_row = row_rel_err(g, dM, ROW_GRAD_NORM[precision])
+    # the last four columns of every row on their own (the quad that straddles V when V % 4 != 0), against their own largest |dM|
+    q0 = max(0, V - 4)
+    err_quad = np.abs(g[:, q0:] - dM[:, q0:]).max(axis=1) / np.abs(dM[:, q0:]).max()
+    out["grad"] = float(err_row.max())
+    out["grad_quad"] = float(err_quad.max())
+    assert out["grad"] <= tol["grad"], f"first-step gradient: row {int(err_row.argmax())}, {out['grad']:.3e} > {tol['grad']:.0e}"
+    assert out["grad_quad"] <= tol["grad"], \
+        f"first-step gradient, last four columns: row {int(err_quad.argmax())}, {out['grad_quad']:.3e} > {tol['grad']:.0e}"
+    # ---- n epochs
+    for _ in range(n - 1):
+        terms, _ = _oracle_adam_step(o, eps, lr)
+        for k in hist_o:
+            hist_o[k].append(terms.get(k, np.nan))
+    e.step(n - 1, lr, hist, 1)
+    h = hist.cpu().numpy().astype(np.float64)
+    cols = [(_capi.H_TOTAL, "total_loss"), (_capi.H_MAIN, "main_loss"), (_capi.H_VG, "vg_reg"), (_capi.H_KL, "kl_reg")]
+    if "lambda_r" in lam:
+        cols.append((_capi.H_ENTROPY, "entropy_reg"))
+    if variant == "constrained":
+        cols += [(_capi.H_COUNT, "count_reg"), (_capi.H_FREG, "lambda_f_reg")]
+    for col, k in cols:
+        ref = np.array([float(x) for x in hist_o[k]])
+        err = float(np.abs(h[:, col] - ref).max())
+        assert err <= TOL[precision]["loss"] * max(1.0, float(np.abs(ref).max())), f"{k}: max per-epoch |delta| {err:.3e}"
+    if variant == "constrained":
+        P, Fg = e.result(with_filter=True)
+    else:
+        P = e.result()
+    P = P.cpu().numpy().astype(np.float64)
+    Po = orc.softmax_rows(o.M)
+    out["P"] = float((np.abs(P - Po) / Po).max())
+    assert out["P"] <= tol["P"], f"max|P - Po| / Po = {out['P']:.3e} > {tol['P']:.0e}"
+    bc2 = np.sqrt(1.0 - 0.999 ** n)
+
+    def den_err(v, vo):
+        den, deno = np.sqrt(v) / bc2 + eps, np.sqrt(vo) / bc2 + eps
+        return float((np.abs(den - deno) / deno).max())
+    vo = o.vM if variant == "constrained" else o.v
+    out["den"] = den_err(m2[:, :V].cpu().numpy().astype(np.float64), vo)
+    assert out["den"] <= tol["den"], f"second moment (Adam's denominator): {out['den']:.3e} > {tol['den']:.0e}"
+    if variant == "constrained":
+        fs = e.filter_state().cpu().numpy().astype(np.float64)
+        out["F"] = float((np.abs(fs[0, :C] - o.F) / np.maximum(1.0, np.abs(o.F))).max())
+        out["F_den"] = den_err(fs[2, :C], o.vF)
+        fo = 1.0 / (1.0 + np.exp(-o.F))
+        assert float(np.abs(Fg.cpu().numpy() - fo).max()) <= tol["P"]
+        assert out["F"] <= tol["P"], f"filter logits: {out['F']:.3e}"
+        assert float(np.abs(fs[1, :C] - o.mF).max()) <= tol["grad"] * float(np.abs(o.mF).max()), "filter first moment"
+        assert out["F_den"] <= tol["den"], f"filter second moment: {out['F_den']:.3e}"
+        assert np.array_equal(e.filter_state()[:, C:].cpu().numpy(), fpad0), "filter padding changed"
+    # ---- padding: the columns [V, pitch) of M and both moments hold what they held after create
+    for name, x, x0 in zip(("M", "exp_avg", "exp_avg_sq"), (M, m1, m2), pad0):
+        assert x.shape[1] == pitch
+        assert np.array_equal(x[:, V:].cpu().numpy(), x0), f"padding of {name} changed"
+    e.release()
+    return out

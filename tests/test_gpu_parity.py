@@ -271,9 +271,12 @@ def test_project_genes_full_size_linearity_cfg2():
 @pytest.mark.parametrize("V", [1023, 2049, 4100, 8200, 12500, 16384, 16385, 20000])
 @pytest.mark.parametrize("variant", ["plain", "regularised", "constrained"])
 def test_update_kernel_row_lengths(V, variant):
-    """The fused row-dot + Adam kernel keeps a whole row of M, X and both moments in registers; its instantiations
-    (256 or 512 threads x 1..8 float4 per array) and the two-kernel fallback for rows longer than 16 384 spots must all
-    reproduce the fp64 oracle (loss trajectory, mapping, filter)."""
+    """The row-length test of the clusters path: 24 cells and at most 16 384 spots train on the clusters-mode kernels (tg_sc_forward /
+    tg_sc_backward, then the update with X in fp32), beyond 16 384 spots on the GEMM path's backward with the row-dot epilogue and the
+    1 024-thread tg_adam_update; asserted through tg_debug_layout(...)[7].  Loss trajectory, mapping and filter against the fp64
+    oracle.  The GEMM path's update kernels at every row length (every tg_adam_rowpass / tg_adam_update instantiation, X in bf16
+    included) are tests/test_update_row_lengths.py (emulator) and tests/test_gpu_update_row_lengths.py."""
+    import ctypes as ct
     from oracle import tangram_oracle as orc
     from tangram_amd.engine import HipMapperEngine
     from tangram_amd import _capi
@@ -295,6 +298,9 @@ def test_update_kernel_row_lengths(V, variant):
             lam.update(lambda_r=1e-3, lambda_l1=1e-4, lambda_l2=1e-5)
         e = HipMapperEngine(S, G, M0, d=d, device=DEV, precision="fp32", lambdas=lam)
         o = orc.OracleMapper(S, G, d=d, M0=M0, dtype=np.float64, **lam)
+    geo = (ct.c_int * 8)()
+    assert e._lib.tg_debug_layout(ct.byref(e.cfg), geo) == 0
+    assert geo[7] == int(V <= 16384), "clusters-mode kernels up to 16 384 spots, the GEMM path beyond"
     hist = e.new_history(n)
     e.step(n, 0.1, hist)
     res = o.train(n, 0.1)
