@@ -9,7 +9,8 @@ The fixtures travel to the GPU box; the reference does not.
 
 Each fixture stores the inputs' generator parameters (inputs are regenerated from the seed by
 oracle.tangram_oracle.make_synthetic), the initial logits, the per-epoch history, the final
-mapping P, the final projection P^T S, and the first-step gradient dM.
+mapping P, the final projection P^T S, and the first-step gradient dM; the spatial cases generated since the irregular-graph
+fixtures also store the first step's individual spatial term values (term_*).
 """
 import importlib.util
 import os
@@ -20,7 +21,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
-from oracle.tangram_oracle import make_synthetic, grid_graph  # noqa: E402
+from oracle.tangram_oracle import make_synthetic, grid_graph, irregular_graph  # noqa: E402
 
 REF = "/root/reference/tangram/mapping_optimizer.py"
 OUT = os.path.join(os.path.dirname(HERE), "tests", "golden")
@@ -37,6 +38,12 @@ CASES = {
                       dict(lambda_g1=1, lambda_d=1, lambda_neighborhood_g1=0.96, lambda_ct_islands=0.17)),
     "cells_autocorr": (80, 20, 36, 10, 30, "autocorr",
                        dict(lambda_g1=1, lambda_d=1, lambda_getis_ord=0.6, lambda_moran=0.4, lambda_geary=0.3)),
+    # the same terms on an irregular, asymmetric, distance-weighted spot graph (oracle.tangram_oracle.irregular_graph: empty rows,
+    # an empty column, rows of 8 / 9 / 16 / 17 non-zeros, a hub); `graph` is popped by build_inputs
+    "cells_spatial_irregular": (220, 36, 130, 12, 36, "spatial",
+                                dict(lambda_g1=1, lambda_d=1, lambda_neighborhood_g1=0.96, lambda_ct_islands=0.17, graph="irregular")),
+    "cells_autocorr_irregular": (180, 32, 110, 13, 32, "autocorr",
+                                 dict(lambda_g1=1, lambda_d=1, lambda_getis_ord=0.6, lambda_moran=0.4, lambda_geary=0.3, graph="irregular")),
     "cells_val": (100, 24, 40, 9, 20, "cells", dict(lambda_g1=1, lambda_d=1, lambda_g2=0.5, val_each=2)),
     "constrained": (150, 40, 60, 7, 50, "constrained",
                     dict(lambda_d=1, lambda_g1=1, lambda_g2=1, lambda_count=1, lambda_f_reg=1, target_count=40)),
@@ -56,6 +63,10 @@ CASES = {
     "grid_g2_0_d1_rna_scaled": (12, 60, 80, 11, 500, "grid", dict(lambda_g1=1, lambda_g2=0, lambda_d=1, prior="rna_count_based", scale=True)),
     "grid_g2_0_d1_rna_unscaled": (12, 60, 80, 11, 500, "grid", dict(lambda_g1=1, lambda_g2=0, lambda_d=1, prior="rna_count_based", scale=False)),
 }
+# Mapper.__init__ computes the autocorrelation references of G (mapping_optimizer.py:144) before to_double() can cast anything, so
+# the "fp64" run of cells_autocorr compares against references built in fp32 (why tests/test_oracle_golden.py is looser on that
+# case).  The cases listed here call the reference's own _spatial_local_indicators again after the cast: a true fp64 run.
+FP64_INDICATORS = {"cells_autocorr_irregular"}
 GRID_CELLS = 360
 RANDOM_STATE = 42
 
@@ -90,6 +101,11 @@ def cluster_inputs(n_clusters, K, V, seed, scale, prior):
 def build_inputs(name):
     C, K, V, seed, epochs, mode, kw = CASES[name]
     kw = dict(kw)
+    if kw.pop("graph", "grid") == "irregular":
+        def graph(V, standardized, self_inclusion):
+            return irregular_graph(V, seed, standardized, self_inclusion, binary=not standardized and not self_inclusion)
+    else:
+        graph = grid_graph
     if mode == "grid":
         ci = cluster_inputs(C, K, V, seed, kw.pop("scale"), kw.pop("prior"))
         args = dict(S=ci["S"], G=ci["G"], d=ci["d"], d_source=ci["d_source"])
@@ -106,12 +122,12 @@ def build_inputs(name):
         ds = rng.random(C).astype(np.float32)
         args["d_source"] = ds / ds.sum()
     if mode == "spatial":
-        args["voxel_weights"] = grid_graph(V, standardized=True, self_inclusion=True)
-        args["neighborhood_filter"] = grid_graph(V, standardized=False, self_inclusion=False)
+        args["voxel_weights"] = graph(V, standardized=True, self_inclusion=True)
+        args["neighborhood_filter"] = graph(V, standardized=False, self_inclusion=False)
         args["ct_encode"] = data["ct_encode"]
     if mode == "autocorr":
         # one matrix serves all three indicators in the reference (mapping_optimizer.py:139-141); row-standardised, no self loops
-        args["spatial_weights"] = grid_graph(V, standardized=True, self_inclusion=False)
+        args["spatial_weights"] = graph(V, standardized=True, self_inclusion=False)
     args.update(kw)
     return args, epochs, mode
 
@@ -127,6 +143,29 @@ def to_double(mapper):
         pass  # None for the cases used here
 
 
+# the individual spatial term values of Mapper._loss_fn (mapping_optimizer.py:237-263): locals of the reference's function -- its
+# return tuple and its train() history drop them -- under the names the oracle's `terms` uses
+TERM_LOCALS = dict(nb_sim="gv_neighborhood_sim", ct_island="ct_island_penalty", getis_sim="getis_ord_sim", moran_sim="moran_sim",
+                   geary_sim="gearys_sim")
+
+
+def first_step_terms(mapper):
+    """Run the reference's _loss_fn once and read the term values it computes from the returning frame (no restatement)."""
+    got = {}
+
+    def prof(frame, event, arg):
+        if event == "return" and frame.f_code.co_name == "_loss_fn":
+            for k, local in TERM_LOCALS.items():
+                got[k] = float(frame.f_locals[local])
+
+    sys.setprofile(prof)
+    try:
+        loss = mapper._loss_fn(verbose=False)[0]
+    finally:
+        sys.setprofile(None)
+    return loss, got
+
+
 def run(mo, name, double):
     args, epochs, mode = build_inputs(name)
     val_each = args.pop("val_each", None)
@@ -134,10 +173,16 @@ def run(mo, name, double):
     mapper = cls(device="cpu", random_state=RANDOM_STATE, **args)
     if double:
         to_double(mapper)
+        if name in FP64_INDICATORS:
+            mapper.getis_ord_G_star_ref, mapper.moran_I_ref, mapper.gearys_C_ref = mapper._spatial_local_indicators(mapper.G_train)
     M0 = mapper.M.detach().numpy().astype(np.float32).copy()
     F0 = mapper.F.detach().numpy().astype(np.float32).copy() if mode == "constrained" else None
     # first-step gradient
-    loss = mapper._loss_fn(verbose=False)[0]
+    terms = {}
+    if mode in ("spatial", "autocorr"):
+        loss, terms = first_step_terms(mapper)
+    else:
+        loss = mapper._loss_fn(verbose=False)[0]
     loss.backward()
     dM0 = mapper.M.grad.detach().numpy().copy()
     dF0 = mapper.F.grad.detach().numpy().copy() if mode == "constrained" else None
@@ -149,6 +194,9 @@ def run(mo, name, double):
     else:
         res = mapper.train(num_epochs=epochs, learning_rate=0.1, print_each=None)
     out = dict(M0=M0, dM0=dM0, P=res[0])
+    for k, v in terms.items():
+        if not np.isnan(v):
+            out["term_" + k] = np.float64(v)
     if mode == "constrained":
         out.update(F0=F0, dF0=dF0, F_out=res[1])
         hist = res[2]

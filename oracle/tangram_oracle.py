@@ -455,3 +455,74 @@ def grid_graph(V, standardized, self_inclusion):
     if self_inclusion:
         W = W + np.eye(V, dtype=np.float32)
     return W
+
+
+# named rows of irregular_graph: row index -> forced number of non-zeros (before the identity is added); the hub is the last row
+IRREGULAR_ROW_LENGTHS = {0: 0, 1: 1, 2: 7, 3: 8, 4: 9, 5: 16, 6: 17}
+IRREGULAR_HUB_MIN = 40
+IRREGULAR_MIN_V = 64
+
+
+def irregular_graph(V, seed, standardized, self_inclusion, binary=False):
+    """Dense V x V float32 weights of an irregular, asymmetric spot graph (what kNN / radius / Delaunay graphs on real tissue
+    look like to the CSR kernels, unlike the lattices of grid_graph):
+
+    - spots at seeded random positions in the unit square; spot v points at its k_v nearest neighbours, k_v drawn per spot
+      from 2 .. 12, so the pattern is asymmetric and the degrees vary;
+    - rows 0 .. 6 have exactly 0, 1, 7, 8, 9, 16 and 17 non-zeros (IRREGULAR_ROW_LENGTHS), the last row is a hub with
+      max(IRREGULAR_HUB_MIN, V // 8) of them (its nearest spots); column 0 is empty (no spot points at spot 0, which is itself
+      isolated) and the diagonal is empty;
+    - weights 1 / (1 + 10 * distance) -- all different within a row -- or 1 with `binary`; `standardized` divides each row by
+      its sum and leaves empty rows empty; `self_inclusion` adds the identity afterwards (spatial_weights.py:5-29 order).
+
+    The pattern and the positions depend on (V, seed) only: the three variants of one (V, seed) share their pattern."""
+    if V < IRREGULAR_MIN_V:
+        raise ValueError(f"irregular_graph needs at least {IRREGULAR_MIN_V} spots")
+    rng = np.random.default_rng(seed)
+    pos = rng.random((V, 2))
+    k = rng.integers(2, 13, size=V)
+    for v, n in IRREGULAR_ROW_LENGTHS.items():
+        k[v] = n
+    k[V - 1] = max(IRREGULAR_HUB_MIN, V // 8)
+    dist = np.sqrt(((pos[:, None, :] - pos[None, :, :]) ** 2).sum(axis=2))
+    cand = dist.copy()
+    np.fill_diagonal(cand, np.inf)
+    cand[:, 0] = np.inf                                        # nobody points at spot 0: an empty column
+    order = np.argsort(cand, axis=1, kind="stable")
+    W = np.zeros((V, V), dtype=np.float64)
+    for v in range(V):
+        nb = order[v, :k[v]]
+        W[v, nb] = 1.0 if binary else 1.0 / (1.0 + 10.0 * dist[v, nb])
+    if standardized:
+        rs = W.sum(axis=1, keepdims=True)
+        rs[rs == 0] = 1
+        W = W / rs
+    if self_inclusion:
+        W = W + np.eye(V)
+    return W.astype(np.float32)
+
+
+def ring_graph(V, n, seed):
+    """Dense V x V float32 weights of the directed ring v -> v+1 .. v+n (mod V) with seeded, unequal weights in [0.5, 1.5):
+    every row and every column has exactly n non-zeros, the pattern is asymmetric (n < V / 2)."""
+    rng = np.random.default_rng(seed)
+    W = np.zeros((V, V), dtype=np.float32)
+    for v in range(V):
+        W[v, (v + 1 + np.arange(n)) % V] = 0.5 + rng.random(n)
+    return W
+
+
+def star_graph(V, centre, outward, seed):
+    """Dense V x V float32 weights of an asymmetric star with seeded, unequal weights.  outward=True: the centre row points
+    at every other spot and every other row is empty (one non-empty row; the transpose has one non-empty column).
+    outward=False: every row has at least one non-zero (spot v points at the centre, the centre at its successor) while the
+    transpose has V - 2 empty rows."""
+    rng = np.random.default_rng(seed)
+    W = np.zeros((V, V), dtype=np.float32)
+    others = np.array([v for v in range(V) if v != centre])
+    if outward:
+        W[centre, others] = 0.5 + rng.random(V - 1)
+    else:
+        W[others, centre] = 0.5 + rng.random(V - 1)
+        W[centre, (centre + 1) % V] = 0.75
+    return W

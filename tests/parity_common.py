@@ -391,3 +391,308 @@ def update_row_case(device, C, K, V, variant, precision, tile=0, expect_tile=128
         assert np.array_equal(x[:, V:].cpu().numpy(), x0), f"padding of {name} changed"
     e.release()
     return out
+
+
+# ---- the CSR spatial-term kernels on irregular, weighted, asymmetric spot graphs (tests/test_spatial_graphs.py on the emulator,
+# tests/test_gpu_spatial_graphs.py on the GPU) ----------------------------------------------------------------------------------
+BETA1 = 0.9
+
+
+def _grad_from_first_moment(eng, V):
+    _, m1, _, _ = eng.logits()
+    return m1[:, :V] / (1.0 - BETA1)            # exp_avg after one step = (1 - beta1) * grad
+
+
+# term -> (lambda name, lambda of these kernel tests, history column name in _capi, the oracle's name of the term value).
+# The lambdas are far above the tutorial's where the term is otherwise a vanishing share of the gradient (islands at 0.17 are
+# 0.3 % of the gradient norm on the irregular graph, 4 % at 10; Geary at 0.3 is 3 %): every term has to be at least a tenth of the gradient for its own
+# error to be visible (spatial_graph_case asserts that share on the oracle).
+SPATIAL_TERMS = {
+    "nb":    ("lambda_neighborhood_g1", 0.96, "H_NB", "nb_sim"),
+    "ct":    ("lambda_ct_islands", 40.0, "H_CT", "ct_island"),
+    "getis": ("lambda_getis_ord", 0.5, "H_GETIS", "getis_sim"),
+    "moran": ("lambda_moran", 0.4, "H_MORAN", "moran_sim"),
+    "geary": ("lambda_geary", 3.0, "H_GEARY", "geary_sim"),
+}
+ALL_FIVE = ("nb", "ct", "getis", "moran", "geary")
+GRAD_TOL = 1e-5                  # first-step gradient, relative Frobenius norm (the bound of the existing spatial GPU tests)
+PART_TOL = 2e-4                  # spatial part of the gradient: 2 * GRAD_TOL / share with share >= MIN_SHARE
+MIN_SHARE = 0.1
+
+
+def _row_standardised(W):
+    rs = W.sum(axis=1, keepdims=True)
+    rs[rs == 0] = 1
+    return (W / rs).astype(np.float32)
+
+
+def spatial_graphs(graph, V, seed):
+    """The three dense float32 spot graphs of one case: voxel_weights (row-standardised + identity), neighborhood_filter,
+    spatial_weights (row-standardised, no self loops) -- spatial_weights.py:5-29 roles -- on the pattern named by `graph`:
+    "irregular" (oracle.tangram_oracle.irregular_graph), "ring<n>" (every row exactly n unequal non-zeros, asymmetric),
+    "star_out" (all rows empty but one), "star_in" (no empty row, the transpose has V - 2 empty rows)."""
+    from oracle import tangram_oracle as orc
+    if graph == "irregular":
+        return dict(voxel_weights=orc.irregular_graph(V, seed, True, True),
+                    neighborhood_filter=orc.irregular_graph(V, seed, False, False, binary=True),
+                    spatial_weights=orc.irregular_graph(V, seed, True, False))
+    if graph.startswith("ring"):
+        n = int(graph[4:])
+        R = orc.ring_graph(V, n, seed)
+        Nf = (R / np.float32(n)).astype(np.float32)               # unequal weights, row sums about 1: D = ct - N ct changes sign
+    else:
+        R = orc.star_graph(V, V // 3, graph == "star_out", seed)
+        Nf = _row_standardised(R) if graph == "star_out" else R
+    Ws = _row_standardised(R)
+    return dict(voxel_weights=Ws + np.eye(V, dtype=np.float32), neighborhood_filter=Nf, spatial_weights=Ws)
+
+
+def spatial_problem(C, K, V, T, graph, terms, seed):
+    """(data, M0, lambdas, graph keywords of the enabled terms) of one spatial case."""
+    from oracle import tangram_oracle as orc
+    data = orc.make_synthetic(C, K, V, seed=seed, n_types=T)
+    M0 = orc.reference_init_M(C, V, seed + 1)
+    lam = dict(lambda_g1=1.0, lambda_d=1.0)
+    for t in terms:
+        lam[SPATIAL_TERMS[t][0]] = SPATIAL_TERMS[t][1]
+    g = spatial_graphs(graph, V, seed)
+    kw = {}
+    if "nb" in terms:
+        kw["voxel_weights"] = g["voxel_weights"]
+    if "ct" in terms:
+        kw.update(neighborhood_filter=g["neighborhood_filter"], ct_encode=data["ct_encode"])
+    if set(terms) & {"getis", "moran", "geary"}:
+        kw["spatial_weights"] = g["spatial_weights"]
+    return data, M0, lam, kw
+
+
+def spatial_oracle(C, K, V, T, graph, terms, seed, n=3):
+    """fp64 oracle of one spatial case: per-epoch terms, the mapping after n epochs, the first-step gradient with the
+    spatial terms and without them, and the spatial share of the gradient."""
+    from oracle import tangram_oracle as orc
+    data, M0, lam, kw = spatial_problem(C, K, V, T, graph, terms, seed)
+    o = orc.OracleMapper(data["S"], data["G"], d=data["d"], M0=M0, dtype=np.float64, **lam, **kw)
+    hist, dM = [], None
+    for i in range(n):
+        _, g = o.loss_and_grad()
+        if i == 0:
+            dM = g.copy()
+        hist.append(o.step(0.1))
+    base = {k: v for k, v in lam.items() if k in ("lambda_g1", "lambda_d")}
+    _, dM0 = orc.OracleMapper(data["S"], data["G"], d=data["d"], M0=M0, dtype=np.float64, **base).loss_and_grad()
+    share = float(np.linalg.norm(dM - dM0) / np.linalg.norm(dM))
+    return dict(hist=hist, P=orc.softmax_rows(o.M), dM=dM, dM0=dM0, share=share)
+
+
+def _engine_graphs(kw, csr):
+    import scipy.sparse as sp
+    return {k: (sp.csr_matrix(v) if csr and k != "ct_encode" else v) for k, v in kw.items()}
+
+
+def spatial_graph_case(device, C, K, V, T, graph, terms, precision, tile=0, csr=False, seed=0, n=3, ref=None, part=True):
+    """One problem with CSR spatial terms through the C ABI against the fp64 oracle, n epochs; returns the measured errors.
+
+    Checks: every enabled history column -- total, main, KL and each spatial term's own column -- at TOL[precision]["loss"]; the
+    mapping at TOL[precision]["P"]; the first-step gradient (Adam's first moment) at GRAD_TOL relative (1e-2 in plain bf16, the
+    bound of tests/test_gpu_production_tiles.py); and, for `part`, the SPATIAL PART of the gradient by itself: engine and oracle
+    run a second time with the spatial lambdas at 0, g_with - g_without is compared on both sides relative to the oracle's
+    |g_with - g_without|.  Two gradients each within GRAD_TOL |g| differ from the truth's difference by at most 2 GRAD_TOL |g| =
+    2 GRAD_TOL / share relative, share = |g_with - g_without| / |g_with|: the oracle's share must be at least MIN_SHARE (a
+    condition on the inputs, evaluated on the checker) and the engine is held to PART_TOL = 2 GRAD_TOL / MIN_SHARE."""
+    from tangram_amd.engine import HipMapperEngine
+    from tangram_amd import _capi
+    tol = TOL[precision]
+    data, M0, lam, kw = spatial_problem(C, K, V, T, graph, terms, seed)
+    ref = ref or spatial_oracle(C, K, V, T, graph, terms, seed, n)
+    e = HipMapperEngine(data["S"], data["G"], M0, d=data["d"], device=device, precision=precision, lambdas=lam, tile_size=tile,
+                        **_engine_graphs(kw, csr))
+    hist = e.new_history(n)
+    e.step(1, 0.1, hist, 0)
+    g = _grad_from_first_moment(e, V).cpu().numpy().astype(np.float64)
+    e.step(n - 1, 0.1, hist, 1)
+    h = hist.cpu().numpy().astype(np.float64)
+    P = e.result().cpu().numpy().astype(np.float64)
+    e.release()
+    out = dict(share=ref["share"])
+    out["grad"] = float(np.linalg.norm(g - ref["dM"]) / np.linalg.norm(ref["dM"]))
+    cols = [(_capi.H_TOTAL, "total_loss"), (_capi.H_MAIN, "main_loss"), (_capi.H_KL, "kl_reg")]
+    cols += [(getattr(_capi, SPATIAL_TERMS[t][2]), SPATIAL_TERMS[t][3]) for t in terms]
+    out["loss"] = {}
+    for col, k in cols:
+        r = np.array([float(x[k]) for x in ref["hist"]])
+        out["loss"][k] = float(np.abs(h[:, col] - r).max() / max(1.0, float(np.abs(r).max())))
+    out["P"] = float(np.abs(P - ref["P"]).max())
+    if part:
+        base = {k: v for k, v in lam.items() if k in ("lambda_g1", "lambda_d")}
+        e0 = HipMapperEngine(data["S"], data["G"], M0, d=data["d"], device=device, precision=precision, lambdas=base, tile_size=tile)
+        e0.step(1, 0.1, e0.new_history(1), 0)
+        g0 = _grad_from_first_moment(e0, V).cpu().numpy().astype(np.float64)
+        e0.release()
+        d_ref = ref["dM"] - ref["dM0"]
+        out["part"] = float(np.linalg.norm((g - g0) - d_ref) / np.linalg.norm(d_ref))
+    print(f"spatial case C{C} K{K} V{V} T{T} {graph} {'+'.join(terms)} {precision} tile{tile} csr{int(csr)}: {out}")
+    if part:
+        assert ref["share"] >= MIN_SHARE, f"inputs: the spatial terms are only {ref['share']:.3f} of the oracle's gradient"
+    for k, err in out["loss"].items():
+        assert err <= tol["loss"], f"{k}: max per-epoch |delta| {err:.3e} > {tol['loss']:.0e}"
+    assert out["P"] <= tol["P"], f"max|dP| {out['P']:.3e} > {tol['P']:.0e}"
+    gtol = 1e-2 if precision == "bf16" else GRAD_TOL
+    assert out["grad"] <= gtol, f"first-step gradient rel err {out['grad']:.3e} > {gtol:.0e}"
+    if part:
+        ptol = PART_TOL * (gtol / GRAD_TOL)
+        assert out["part"] <= ptol, f"spatial part of the first-step gradient rel err {out['part']:.3e} > {ptol:.0e}"
+    return out
+
+
+def spatial_cases(gpu):
+    """The shared case table: (id, C, K, V, T, graph, terms, tile_size, csr).  The emulated table uses smaller C / V where the
+    emulator's time demands and keeps every edge; the edge is named in the id."""
+    big = gpu
+    out = []
+    C, K, V = 300, 50, 501                                        # 501 spots: not a multiple of 8 (the XCD bands of tg_spmm are unequal)
+    for i, terms in enumerate([(t,) for t in ALL_FIVE] + [ALL_FIVE]):
+        out.append((f"irregular-{'all5' if len(terms) == 5 else terms[0]}", C, K, V, 9, "irregular", terms, 0, i % 2 == 0))
+    # every row exactly n non-zeros: one full trip of tg_spmm's eight-at-a-time loop, one past it, two full trips, one past them
+    for i, nnz in enumerate((8, 9, 16, 17)):
+        out.append((f"ring-rows-of-{nnz}", 300 if big else 60, 50 if big else 24, 131, 5, f"ring{nnz}", ALL_FIVE, 0, i % 2 == 1))
+    out.append(("star-all-rows-empty-but-one", 300 if big else 60, 50 if big else 24, 67, 5, "star_out", ALL_FIVE, 0, True))
+    out.append(("star-transpose-has-empty-rows", 300 if big else 60, 50 if big else 24, 67, 5, "star_in", ALL_FIVE, 0, False))
+    # second trip of the gene strides of tg_spmm (4 x 256 genes per trip) and tg_ac_finalize (1 024 threads); 1 025 and 1 030: a ragged
+    # last quad on the second trip
+    for i, Kg in enumerate((1021, 1024, 1025, 1030, 2000)):
+        out.append((f"genes-{Kg}-second-stride-trip", 500 if big else 40, Kg, 3000 if big else 100, 5, "irregular", ALL_FIVE, 0, i % 2 == 0))
+    out.append(("genes-6200-all-genes-width", 300 if big else 33, 6200, 600 if big else 64, 5, "irregular", ALL_FIVE, 0, True))
+    # cell types: the 64-thread stride of tg_ct_mask / tg_ct_grad (63, 64, 65, 130 types) and K + 1 + T below / at / above a multiple
+    # of the tile on both layouts (Kp = K + 1 + T rounded up to the tile: tg_make_layout)
+    for i, (Kg, T, tile) in enumerate(((63, 63, 128), (63, 64, 128), (63, 65, 128), (124, 130, 256), (125, 130, 256), (126, 130, 256))):
+        for terms in (("ct",), ("nb", "ct")):
+            out.append((f"types-{T}-aug-{Kg + 1 + T}-tile{tile}-{'+'.join(terms)}", 300, Kg, 70, T, "irregular", terms, tile, (i + len(terms)) % 2 == 0))
+    # TG_RB = 16 spots per block of the per-gene partial kernels (tg_colstats, tg_ac_stats1/2, tg_ac_grad, tg_ac_refs)
+    for i, Vs in enumerate((15, 16, 17, 33)):
+        out.append((f"spots-{Vs}-row-block-of-16", 40, 20, Vs, 3, "ring9", ALL_FIVE, 0, i % 2 == 0))
+    if gpu:
+        out.append(("autocorr-at-size", 500, 257, 3000, 0, "irregular", ("getis", "moran", "geary"), 0, True))
+    return out
+
+
+def spatial_shards_case(device, precision, world=3, n=3, seed=11):
+    """All five terms on `world` spot shards (threads, tests/local_comm.py) of the 1 001-spot irregular graph -- every shard
+    gathers Ghat and evaluates the whole graph, the hub row reads rows of every shard -- against the single engine and the
+    fp64 oracle (the comparisons of test_spatial_terms_on_spot_shards_match_single_engine, every spatial column included)."""
+    from tangram_amd.engine import HipMapperEngine
+    from tangram_amd.sharded import make_sharded
+    from tangram_amd import _capi
+    from tests.local_comm import run_ranks
+    C, K, V, T = 120, 24, 1001, 5
+    data, M0, lam, kw = spatial_problem(C, K, V, T, "irregular", ALL_FIVE, seed)
+    graphs = _engine_graphs(kw, True)
+
+    def rank_fn(comm):
+        sh = make_sharded(data["S"], data["G"], M0, d=data["d"], device=device, precision=precision, lambdas=lam, comm=comm, **graphs)
+        hist = sh.eng.new_history(n)
+        sh.run(n, 0.1, hist)
+        out = hist.cpu().numpy(), sh.result_full().cpu().numpy()
+        sh.release()
+        return out
+
+    res = run_ranks(world, rank_fn)
+    e = HipMapperEngine(data["S"], data["G"], M0, d=data["d"], device=device, precision=precision, lambdas=lam, **graphs)
+    h1 = e.new_history(n)
+    e.step(n, 0.1, h1)
+    h1, P1 = h1.cpu().numpy(), e.result().cpu().numpy()
+    e.release()
+    ref = spatial_oracle(C, K, V, T, "irregular", ALL_FIVE, seed, n)
+    names = [(_capi.H_TOTAL, "total_loss"), (_capi.H_MAIN, "main_loss"), (_capi.H_KL, "kl_reg")]
+    names += [(getattr(_capi, SPATIAL_TERMS[t][2]), SPATIAL_TERMS[t][3]) for t in ALL_FIVE]
+    cols = [c for c, _ in names]
+    tol = TOL[precision]
+    for hist, P in res:
+        np.testing.assert_array_equal(hist, res[0][0])                         # the same global history on every rank
+        np.testing.assert_allclose(hist[:, cols], h1[:, cols], atol=5e-6, rtol=2e-6)
+        np.testing.assert_allclose(P, P1, atol=2e-6)
+        for col, k in names:
+            r = np.array([float(x[k]) for x in ref["hist"]])
+            err = float(np.abs(hist[:, col] - r).max())
+            assert err <= tol["loss"] * max(1.0, float(np.abs(r).max())), f"{k}: max per-epoch |delta| {err:.3e}"
+        assert float(np.abs(P - ref["P"]).max()) <= tol["P"]
+
+
+def _run_engine(device, precision, data, M0, lam, graphs, n=3):
+    from tangram_amd.engine import HipMapperEngine
+    e = HipMapperEngine(data["S"], data["G"], M0, d=data["d"], device=device, precision=precision, lambdas=lam, **graphs)
+    hist = e.new_history(n)
+    e.step(n, 0.1, hist)
+    out = hist.cpu().numpy(), e.result().cpu().numpy()
+    e.release()
+    return out
+
+
+def spatial_csr_input_case(device, precision, seed=5):
+    """The spot graphs as a caller may hand them: unsorted indices, explicit zeros, int64 indices, float64 data, csc / coo format give
+    the same history and mapping as the canonical float32 CSR matrix, bit for bit; duplicate entries (summed by the conversion, in
+    another order) within TOL."""
+    import scipy.sparse as sp
+    C, K, V, T = 80, 24, 131, 5
+    data, M0, lam, kw = spatial_problem(C, K, V, T, "irregular", ALL_FIVE, seed)
+    gk = [k for k in kw if k != "ct_encode"]
+    canon = {k: sp.csr_matrix(kw[k]) for k in gk}
+    for m in canon.values():
+        m.sort_indices()
+    h0, P0 = _run_engine(device, precision, data, M0, lam, dict(kw, **canon))
+    rng = np.random.default_rng(seed)
+
+    def unsorted(m):
+        m = m.copy()
+        for v in range(V):
+            b, e = m.indptr[v], m.indptr[v + 1]
+            perm = rng.permutation(e - b)
+            m.indices[b:e], m.data[b:e] = m.indices[b:e][perm], m.data[b:e][perm]
+        m.has_sorted_indices = False
+        return m
+
+    def explicit_zeros(m):
+        coo = m.tocoo()
+        zr, zc = rng.integers(0, V, 3 * V), rng.integers(0, V, 3 * V)
+        free = np.asarray(m[zr, zc]).ravel() == 0
+        zr, zc = zr[free], zc[free]
+        out = sp.coo_matrix((np.concatenate([coo.data, np.zeros(len(zr), np.float32)]),
+                             (np.concatenate([coo.row, zr]), np.concatenate([coo.col, zc]))), shape=(V, V))
+        rows, inv = np.unique(np.stack([out.row, out.col]), axis=1, return_index=True)      # keep one entry per position
+        out = sp.csr_matrix((out.data[inv], (out.row[inv], out.col[inv])), shape=(V, V))
+        assert out.nnz > m.nnz and (out.data == 0).any()
+        return out
+
+    def int64_indices(m):
+        return sp.csr_matrix((m.data, m.indices.astype(np.int64), m.indptr.astype(np.int64)), shape=m.shape)
+
+    def float64_data(m):
+        return sp.csr_matrix((m.data.astype(np.float64), m.indices, m.indptr), shape=m.shape)
+
+    def duplicates(m):
+        coo = m.tocoo()
+        half = (coo.data * np.float32(0.5)).astype(np.float32)
+        return sp.coo_matrix((np.concatenate([half, coo.data - half]), (np.concatenate([coo.row, coo.row]), np.concatenate([coo.col, coo.col]))),
+                             shape=(V, V))
+
+    variants = dict(unsorted=unsorted, explicit_zeros=explicit_zeros, int64_indices=int64_indices, float64_data=float64_data,
+                    csc=lambda m: m.tocsc(), coo=lambda m: m.tocoo())
+    for name, fn in variants.items():
+        h, P = _run_engine(device, precision, data, M0, lam, dict(kw, **{k: fn(canon[k]) for k in gk}))
+        np.testing.assert_array_equal(h, h0, err_msg=name)
+        np.testing.assert_array_equal(P, P0, err_msg=name)
+    h, P = _run_engine(device, precision, data, M0, lam, dict(kw, **{k: duplicates(canon[k]) for k in gk}))
+    tol = TOL[precision]
+    keep = ~np.isnan(h0)
+    assert (np.isnan(h) == np.isnan(h0)).all()
+    assert float(np.abs(h[keep] - h0[keep]).max()) <= tol["loss"] * max(1.0, float(np.abs(h0[keep]).max())), "duplicates: history"
+    assert float(np.abs(P - P0).max()) <= tol["P"], "duplicates: mapping"
+
+
+def spatial_determinism_case(device, precision, seed=7):
+    """Two runs of the all-five irregular case: bit-identical histories and mappings (fixed-order reductions everywhere)."""
+    cid, C, K, V, T, graph, terms, tile, csr = [c for c in spatial_cases(False) if c[0] == "irregular-all5"][0]
+    data, M0, lam, kw = spatial_problem(C, K, V, T, graph, terms, seed)
+    a = _run_engine(device, precision, data, M0, lam, _engine_graphs(kw, True))
+    b = _run_engine(device, precision, data, M0, lam, _engine_graphs(kw, True))
+    np.testing.assert_array_equal(a[0], b[0])
+    np.testing.assert_array_equal(a[1], b[1])

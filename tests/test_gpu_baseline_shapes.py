@@ -23,12 +23,7 @@ from tests import parity_common as pc
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-BETA1 = 0.9
-
-
-def _grad_from_first_moment(eng, V):
-    _, m1, _, _ = eng.logits()
-    return m1[:, :V] / (1.0 - BETA1)            # exp_avg after one step = (1 - beta1) * grad
+from tests.parity_common import BETA1, _grad_from_first_moment  # noqa: E402  (exp_avg after one step = (1 - beta1) * grad)
 
 
 def _check_hist(h, ref, cols, tol=1e-5):

@@ -137,6 +137,29 @@ def test_spatial_extension_terms_with_csr_graph(sim):
     hist = ad_map.uns["training_history"]
     np.testing.assert_allclose([float(x) for x in hist["total_loss"]], ho["total_loss"], atol=1e-5)
     np.testing.assert_allclose(ad_map.X, Po, atol=1e-5)
+    # a second, irregular obsp graph (oracle.tangram_oracle.irregular_graph: asymmetric kNN pattern, empty rows and an empty
+    # column, rows of 8 / 9 / 16 / 17 non-zeros and a hub, unequal distances), all five spatial terms
+    from oracle.spatial_weights_oracle import spatial_weights_oracle
+    V = 70
+    ad_sc, ad_sp = _adatas(C=50, K=10, V=V, seed=4)
+    conn = orc.irregular_graph(V, 4, standardized=False, self_inclusion=False, binary=True)
+    dist = orc.irregular_graph(V, 4, standardized=False, self_inclusion=False)
+    ad_sp.obsp["spatial_connectivities"] = sp.csr_matrix(conn)
+    ad_sp.obsp["spatial_distances"] = sp.csr_matrix(dist)
+    lam = dict(lambda_neighborhood_g1=0.96, lambda_ct_islands=5.0, lambda_getis_ord=0.5, lambda_moran=0.4, lambda_geary=0.3)
+    ad_map = tg.map_cells_to_space(ad_sc, ad_sp, mode="cells", cluster_label="subclass_label", device="cpu", num_epochs=n,
+                                   random_state=42, verbose=False, gemm_precision="fp32", **lam)
+    train = ad_sc.uns["training_genes"]
+    lab = ad_sc.obs["subclass_label"]
+    E = np.stack([(lab == c).to_numpy().astype(np.float32) for c in lab.unique()], axis=1)
+    o = orc.OracleMapper(ad_sc[:, train].X, ad_sp[:, train].X, d=ad_sp.obs["rna_count_based_density"].to_numpy(), lambda_d=1,
+                         voxel_weights=spatial_weights_oracle(conn, dist, True, True), neighborhood_filter=conn, ct_encode=E,
+                         spatial_weights=spatial_weights_oracle(conn, dist, False, True),      # Getis-Ord's matrix wins (mapping_utils.py:326-329)
+                         random_state=42, **lam)
+    Po, ho = o.train(n)
+    hist = ad_map.uns["training_history"]
+    np.testing.assert_allclose([float(x) for x in hist["total_loss"]], ho["total_loss"], atol=1e-5)
+    np.testing.assert_allclose(ad_map.X, Po, atol=1e-5)
 
 
 def test_project_genes_on_device(sim):

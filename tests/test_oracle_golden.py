@@ -51,6 +51,19 @@ def test_first_step_gradient_fp64(golden_dir, name):
         assert np.abs(out[2] - z["f64_dF0"]).max() <= 1e-12
 
 
+@pytest.mark.parametrize("name", [n for n in NAMES if n.endswith("_irregular")])
+def test_first_step_spatial_term_values_fp64(golden_dir, name):
+    """The individual spatial term values of the reference's _loss_fn (locals of its first evaluation, oracle/gen_golden.py:
+    first_step_terms) on the irregular, asymmetric, weighted graph, at the fp64 bound of the trajectory test."""
+    z = _load(golden_dir, name)
+    m, _, mode = _make(name, z, np.float64)
+    terms, _ = m.loss_and_grad()
+    keys = [k[len("f64_term_"):] for k in z.files if k.startswith("f64_term_")]
+    assert set(keys) == ({"nb_sim", "ct_island"} if mode == "spatial" else {"getis_sim", "moran_sim", "geary_sim"})
+    for k in keys:
+        assert abs(float(terms[k]) - float(z["f64_term_" + k])) <= 2e-9, (k, float(terms[k]), float(z["f64_term_" + k]))
+
+
 @pytest.mark.parametrize("name", NAMES)
 def test_trajectory_fp64(golden_dir, name):
     z = _load(golden_dir, name)

@@ -33,6 +33,10 @@ def sim():
     ("cells_val", "bf16x3", 7),          # val_each: validation metrics of _val_loss_fn
     ("cells_spatial", "fp32", 6),
     ("cells_autocorr", "fp32", 6),       # Getis-Ord + Moran + Geary on a CSR spot graph        # neighbourhood-weighted gene term + cell-type islands on a CSR spot graph
+    ("cells_spatial_irregular", "fp32", 6),      # the same terms on the irregular, asymmetric, distance-weighted graph
+    ("cells_spatial_irregular", "bf16x3", 6),
+    ("cells_autocorr_irregular", "fp32", 6),
+    ("cells_autocorr_irregular", "bf16x3", 6),
 ])
 def test_emulated_kernels_match_reference(sim, name, precision, epochs):
     res = pc.run_case(name, "cpu", precision, epochs=epochs)
