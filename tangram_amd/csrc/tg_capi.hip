@@ -11,6 +11,7 @@
 #include <map>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #ifdef TG_SIM
@@ -477,6 +478,65 @@ static void tg_prof_mark(tg_mapper* m, const char* name) {
     m->prof_names.push_back(name);
 }
 
+// ---- kernel variant selection -------------------------------------------------------------------
+// Every map from a handle to the template arguments of a kernel is written ONCE, here: a selector branches on the run-time value and
+// calls `f` with tags that carry the compile-time choice (a type in tg_tag, a number or flag in a std::integral_constant).  `f` is a
+// generic lambda at the launch site; TG_SELECT forces everything inline, down to the branches spelled out below.
+#define TG_SELECT static inline __attribute__((always_inline))
+template <class T> struct tg_tag { using type = T; };
+template <int N> using tg_int = std::integral_constant<int, N>;
+template <bool B> using tg_bool = std::integral_constant<bool, B>;
+
+// the handle's precision code -> PrecF32 / PrecBF16 / PrecBF16x3 / PrecBF16x2S (tg_device.h); returns what f returns
+template <class F>
+TG_SELECT int tg_with_precision(int prec, F&& f) {
+    switch (prec) {
+        case TG_PREC_F32: return f(tg_tag<PrecF32>{});
+        case TG_PREC_BF16: return f(tg_tag<PrecBF16>{});
+        case TG_PREC_BF16X2S: return f(tg_tag<PrecBF16x2S>{});
+        default: return f(tg_tag<PrecBF16x3>{});
+    }
+}
+// tg_mapper_project_genes: a caller's gene block is not known to be bf16-exact, so a handle whose S is projects it on PrecBF16x3.
+// tg_mapper_create prepares the forward kernels of this precision besides the handle's own.
+static inline int tg_project_genes_precision(int prec) { return prec == TG_PREC_BF16X2S ? TG_PREC_BF16X3 : prec; }
+
+// geometry of the forward GEMM (tg_fwd_kernel, tg_fwd_kernel_b): 128 x 512 tiles (split bf16 only), else the layout's square tile
+template <class PR, class F>
+TG_SELECT void tg_with_fwd_geo(const TgLayout& L, F&& f) {
+    if (L.fwd_wide) { if constexpr (PR::NP == 2) f(tg_tag<TgGeoWide>{}); }
+    else if (L.T == 256) f(tg_tag<TgGeoLarge>{});
+    else f(tg_tag<TgGeoSmall>{});
+}
+// square geometry by tile edge: the backward GEMM (tg_bwd_kernel, tg_bwd_kernel_b) and the LDS attributes of a layout (tg_lds_attr)
+template <class F>
+TG_SELECT void tg_with_tile_geo(int tile, F&& f) {
+    if (tile == 256) f(tg_tag<TgGeoLarge>{}); else f(tg_tag<TgGeoSmall>{});
+}
+
+// register-resident update (tg_adam_rowpass, tg_adam_rowpass_b): row length V <= TG_ROWPASS_MAX_V -> (float4 quads per thread, threads)
+template <class F>
+TG_SELECT void tg_with_row_length(int V, F&& f) {
+    if (V <= 4096) {                                  // 256 threads, up to 4 quads each
+        const int nq = (V + 1023) / 1024;
+        if (nq <= 1) f(tg_int<1>{}, tg_int<256>{}); else if (nq <= 2) f(tg_int<2>{}, tg_int<256>{}); else f(tg_int<4>{}, tg_int<256>{});
+    } else {                                          // 512 threads, up to 8 quads each
+        const int nq = (V + 2047) / 2048;
+        if (nq <= 3) f(tg_int<3>{}, tg_int<512>{}); else if (nq <= 4) f(tg_int<4>{}, tg_int<512>{}); else if (nq <= 5) f(tg_int<5>{}, tg_int<512>{});
+        else if (nq <= 6) f(tg_int<6>{}, tg_int<512>{}); else f(tg_int<8>{}, tg_int<512>{});
+    }
+}
+// update kernels: FULL (regulariser row sums), X16 (X stored in bf16) and, with a third flag, STREAM (non-temporal accesses)
+template <class F>
+TG_SELECT void tg_with_update_flags(bool full, bool x16, F&& f) {
+    if (full) { if (x16) f(tg_bool<true>{}, tg_bool<true>{}); else f(tg_bool<true>{}, tg_bool<false>{}); }
+    else { if (x16) f(tg_bool<false>{}, tg_bool<true>{}); else f(tg_bool<false>{}, tg_bool<false>{}); }
+}
+template <class F>
+TG_SELECT void tg_with_update_flags(bool full, bool x16, bool stream, F&& f) {
+    tg_with_update_flags(full, x16, [&](auto fl, auto xh) { if (stream) f(fl, xh, tg_bool<true>{}); else f(fl, xh, tg_bool<false>{}); });
+}
+
 template <class PR, class GE>
 static int tg_lds_attr() {
 #ifndef TG_SIM
@@ -493,6 +553,12 @@ static int tg_lds_attr() {
 #undef TG_BWD_ATTR
 #endif
     return TG_OK;
+}
+template <class PR>
+static int tg_lds_attr_layout(const TgLayout& L) {        // ... of the layout's own tile geometry
+    int rc = TG_OK;
+    tg_with_tile_geo(L.T, [&](auto ge) { rc = tg_lds_attr<PR, typename decltype(ge)::type>(); });
+    return rc;
 }
 
 // small-C path: one switch over the compile-time cluster bound (C rounded up to a multiple of 4) and the per-spot-sums flag
@@ -556,7 +622,7 @@ static int tg_setup_operands(tg_mapper* m, const tg_inputs* in) {
         TG_LAUNCH_CK();
     }
     if (L.T == 256) { const int rc = tg_lds_attr<PR, TgGeoSmall>(); if (rc != TG_OK) return rc; }     // (the backward GEMM may run on 128^2 tiles)
-    return L.T == 256 ? tg_lds_attr<PR, TgGeoLarge>() : tg_lds_attr<PR, TgGeoSmall>();
+    return tg_lds_attr_layout<PR>(L);
 }
 
 static int tg_softmax_stats_from_scratch(tg_mapper* m) {
@@ -812,14 +878,9 @@ extern "C" int tg_mapper_create(const tg_config* cfg, const tg_inputs* in, void*
         if ((rc = tg_s_is_exact(m, in, &exact))) return bail(rc);
         if (exact) { m->cfg.precision = TG_PREC_BF16X2S; m->L.prec = TG_PREC_BF16X2S; }
     }
-    switch (cfg->precision) {
-        case TG_PREC_F32: rc = tg_setup_operands<PrecF32>(m, in); break;
-        case TG_PREC_BF16: rc = tg_setup_operands<PrecBF16>(m, in); break;
-        case TG_PREC_BF16X2S: rc = tg_setup_operands<PrecBF16x2S>(m, in);
-                              if (!rc) rc = L.T == 256 ? tg_lds_attr<PrecBF16x3, TgGeoLarge>() : tg_lds_attr<PrecBF16x3, TgGeoSmall>();   // (tg_mapper_project_genes)
-                              break;
-        default: rc = tg_setup_operands<PrecBF16x3>(m, in); break;
-    }
+    rc = tg_with_precision(cfg->precision, [&](auto pr) { return tg_setup_operands<typename decltype(pr)::type>(m, in); });
+    if (!rc && tg_project_genes_precision(cfg->precision) != cfg->precision)
+        rc = tg_with_precision(tg_project_genes_precision(cfg->precision), [&](auto pr) { return tg_lds_attr_layout<typename decltype(pr)::type>(L); });
     if (rc) return bail(rc);
     // padded G, |G_v|^2, |G_k|^2 partials (reuse genepart as scratch)
     // (genepart [nrb][2][Kp] doubles as scratch: first half |G|^2 partials, second half non-zero counts)
@@ -905,10 +966,10 @@ static int tg_launch_forward(tg_mapper* m, tg_stream_t stream = nullptr, int ban
     if (band < 0) stream = m->stream;
     int grid;
     const TgFwdArgs a = tg_fwd_args<PR>(m, band, St_alt, unfiltered, &grid);
-    if (L.fwd_wide) {
-        if constexpr (PR::NP == 2) TG_LAUNCH((tg_fwd_kernel<PR, TgGeoWide>), grid, 1, TgGeoWide::NT, TgGeoWide::LDS_BYTES, stream, a);
-    } else if (L.T == 256) TG_LAUNCH((tg_fwd_kernel<PR, TgGeoLarge>), grid, 1, TgGeoLarge::NT, TgGeoLarge::LDS_BYTES, stream, a);
-    else TG_LAUNCH((tg_fwd_kernel<PR, TgGeoSmall>), grid, 1, TgGeoSmall::NT, TgGeoSmall::LDS_BYTES, stream, a);
+    tg_with_fwd_geo<PR>(L, [&](auto ge) {
+        using GE = typename decltype(ge)::type;
+        TG_LAUNCH((tg_fwd_kernel<PR, GE>), grid, 1, GE::NT, GE::LDS_BYTES, stream, a);
+    });
     if (band < 0) tg_prof_mark(m, "tg_fwd_kernel");
     return TG_OK;
 }
@@ -923,6 +984,8 @@ static TgGhatReduceArgs tg_ghat_args(tg_mapper* m, bool force_vox) {
     return a;
 }
 
+// many row blocks, e.g. 10 000 spots: tg_gene_reduce_tall(_x), 16 genes x 64 groups per workgroup (another order of the sums)
+static bool tg_gene_reduce_is_tall(int nrb) { return nrb > 512; }
 struct TgPeerLink;
 static int tg_launch_ghat_stats(tg_mapper* m, bool force_vox = false, const TgPeerLink* link = nullptr) {
     const TgLayout& L = m->L;
@@ -931,9 +994,9 @@ static int tg_launch_ghat_stats(tg_mapper* m, bool force_vox = false, const TgPe
     TG_LAUNCH(tg_ghat_reduce, nrb, (L.Kp + TG_GH_COLS - 1) / TG_GH_COLS, 256, 4 * 64 * 2 * 16, m->stream, a);
     tg_prof_mark(m, "tg_ghat_reduce");
     if (link) {                   // spot shard, peer transport: the exchange of the statistics happens inside this kernel
-        if (nrb > 512) TG_LAUNCH(tg_gene_reduce_tall_x, (L.Kp + 15) / 16, 1, 1024, TG_GR_GROUPS * 64 * 2 * 4, m->stream, (const float*)m->fp(L.o_genepart), nrb, L.Kp, m->fp(L.o_genestat), *link);
+        if (tg_gene_reduce_is_tall(nrb)) TG_LAUNCH(tg_gene_reduce_tall_x, (L.Kp + 15) / 16, 1, 1024, TG_GR_GROUPS * 64 * 2 * 4, m->stream, (const float*)m->fp(L.o_genepart), nrb, L.Kp, m->fp(L.o_genestat), *link);
         else TG_LAUNCH(tg_gene_reduce_x, (L.Kp + 63) / 64, 1, 1024, TG_GR_GROUPS * 64 * 2 * 4, m->stream, (const float*)m->fp(L.o_genepart), nrb, L.Kp, m->fp(L.o_genestat), *link);
-    } else if (nrb > 512) {       // many row blocks, e.g. clusters mode on 50 000 spots: 16 genes x 64 groups per workgroup
+    } else if (tg_gene_reduce_is_tall(nrb)) {
         TG_LAUNCH(tg_gene_reduce_tall, (L.Kp + 15) / 16, 1, 1024, TG_GR_GROUPS * 64 * 2 * 4, m->stream, (const float*)m->fp(L.o_genepart), nrb, L.Kp,
                   m->fp(L.o_genestat));
     } else {
@@ -1043,17 +1106,14 @@ static void tg_launch_bwd(tg_mapper* m, tg_stream_t stream, int ct0, int ct1, bo
     if (tile == 0) tile = L.bwd_T;
     const int f = L.T / tile;
     const TgBwdArgs a = tg_bwd_args<PR>(m, f * ct0, f * ct1, &grid, tile);
-#define TG_BWD_GO(GE, F, R, S) TG_LAUNCH((tg_bwd_kernel<PR, GE, F, R, S>), grid, 1, GE::NT, GE::BWD_LDS_BYTES, stream, a)
-    if (tile == 256) {
-        if (x_only) { if (m->stream_once) TG_BWD_GO(TgGeoLarge, false, false, true); else TG_BWD_GO(TgGeoLarge, false, false, false); }
-        else if (L.full) TG_BWD_GO(TgGeoLarge, true, true, true);
-        else TG_BWD_GO(TgGeoLarge, false, true, true);
-    } else {
-        if (x_only) { if (m->stream_once) TG_BWD_GO(TgGeoSmall, false, false, true); else TG_BWD_GO(TgGeoSmall, false, false, false); }
-        else if (L.full) TG_BWD_GO(TgGeoSmall, true, true, true);
-        else TG_BWD_GO(TgGeoSmall, false, true, true);
-    }
+    tg_with_tile_geo(tile, [&](auto ge) {
+        using GE = typename decltype(ge)::type;
+#define TG_BWD_GO(F, R, S) TG_LAUNCH((tg_bwd_kernel<PR, GE, F, R, S>), grid, 1, GE::NT, GE::BWD_LDS_BYTES, stream, a)
+        if (x_only) { if (m->stream_once) TG_BWD_GO(false, false, true); else TG_BWD_GO(false, false, false); }
+        else if (L.full) TG_BWD_GO(true, true, true);
+        else TG_BWD_GO(false, true, true);
 #undef TG_BWD_GO
+    });
 }
 
 static int tg_polling_grid(tg_mapper* m, const void* fn, int nt, int lds, int want);      // (spot-sharded section below)
@@ -1076,6 +1136,10 @@ static void tg_launch_hist_regs(tg_mapper* m, tg_stream_t stream, float* hist_ro
     h.lambda_r = m->cfg.lambda_r; h.lambda_l1 = m->cfg.lambda_l1; h.lambda_l2 = m->cfg.lambda_l2;
     h.constrained = (m->cfg.mode == TG_MODE_CONSTRAINED);
     TG_LAUNCH(tg_hist_regs, 1, 1, 1024, 64, stream, h);
+}
+static void tg_hist_regs_marked(tg_mapper* m, float* hist_row) {      // ... on the handle's stream, with its profile mark
+    tg_launch_hist_regs(m, m->stream, hist_row);
+    tg_prof_mark(m, "tg_hist_regs");
 }
 
 // arguments shared by the update kernels and the row-dot pass, for the cells [c0, c1)
@@ -1111,29 +1175,23 @@ static int tg_launch_rowdots(tg_mapper* m, float* hist_row) {
     tg_prof_mark(m, "tg_bwd_kernel");
     tg_launch_rowsum(m, m->stream, 0, L.C);
     tg_prof_mark(m, "tg_rowsum_parts");
-    if (L.full && !m->fin_pending) {          // (deferred history row: tg_one_step launches this after the update kernel)
-        tg_launch_hist_regs(m, m->stream, hist_row);
-        tg_prof_mark(m, "tg_hist_regs");
-    }
+    if (L.full && !m->fin_pending) tg_hist_regs_marked(m, hist_row);      // (deferred history row: tg_one_step launches this after the update kernel)
     return TG_OK;
+}
+
+// register-resident update of `rows` cell rows (tg_adam_rowpass).  512-thread rows take streaming accesses whatever `stream_once`: with
+// rows that long the cached variant would serve a few hundred cells
+static void tg_launch_rowpass(const TgUpdateArgs& u, bool full, bool x16, bool stream_once, int rows, int V, tg_stream_t stream) {
+    tg_with_update_flags(full, x16, stream_once, [&](auto fl, auto xh, auto so) {
+        tg_with_row_length(V, [&](auto nq, auto nt) {
+            constexpr int NQ = decltype(nq)::value, NT = decltype(nt)::value;
+            TG_LAUNCH((tg_adam_rowpass<decltype(fl)::value, decltype(xh)::value, NQ, NT, (NT == 512 || decltype(so)::value)>), rows, 1, NT, 256, stream, u);
+        });
+    });
 }
 
 // streaming softmax-backward + Adam over the cells [c0, c1); `finalize`: write the next softmax statistics directly
 // (single GPU, no filter)
-template <bool FULL, bool X16, bool STREAM>
-static void tg_launch_rowpass(const TgUpdateArgs& u, int rows, int V, tg_stream_t stream) {
-#define TG_RP(NQ, NT, S) TG_LAUNCH((tg_adam_rowpass<FULL, X16, NQ, NT, S>), rows, 1, NT, 256, stream, u)
-    if (V <= 4096) {                                  // 256 threads, up to 4 quads each
-        const int nq = (V + 1023) / 1024;
-        if (nq <= 1) TG_RP(1, 256, STREAM); else if (nq <= 2) TG_RP(2, 256, STREAM); else TG_RP(4, 256, STREAM);
-    } else {                                          // 512 threads, up to 8 quads each (V <= TG_ROWPASS_MAX_V); streaming accesses
-        const int nq = (V + 2047) / 2048;             // only: with rows this long the cached variant would serve a few hundred cells
-        if (nq <= 3) TG_RP(3, 512, true); else if (nq <= 4) TG_RP(4, 512, true); else if (nq <= 5) TG_RP(5, 512, true);
-        else if (nq <= 6) TG_RP(6, 512, true); else TG_RP(8, 512, true);
-    }
-#undef TG_RP
-}
-
 static int tg_launch_update(tg_mapper* m, float lr, bool finalize, tg_stream_t stream = nullptr, int c0 = 0, int c1 = -1,
                             bool rowpass = false, const TgPeerLink* link = nullptr) {
     const TgLayout& L = m->L;
@@ -1146,20 +1204,16 @@ static int tg_launch_update(tg_mapper* m, float lr, bool finalize, tg_stream_t s
     int extra_wg = 0;
     if (m->fin_pending && whole) { u.fin = m->fin_args; u.fin_on = 1; extra_wg = 1; m->fin_pending = false; }
     if (rowpass) {
-#define TG_RPGO(F, X) do { if (m->stream_once) tg_launch_rowpass<F, X, true>(u, c1 - c0 + extra_wg, L.V, stream); \
-                           else tg_launch_rowpass<F, X, false>(u, c1 - c0 + extra_wg, L.V, stream); } while (0)
-        if (L.full) { if (x16) TG_RPGO(true, true); else TG_RPGO(true, false); }
-        else { if (x16) TG_RPGO(false, true); else TG_RPGO(false, false); }
-#undef TG_RPGO
+        tg_launch_rowpass(u, L.full, x16, m->stream_once, c1 - c0 + extra_wg, L.V, stream);
         if (whole) tg_prof_mark(m, "tg_adam_rowpass");
         return TG_OK;
     }
     const bool few = (c1 - c0) <= 64 && L.V > 4096;      // a handful of long rows: 1 024 threads per cell
-#define TG_AUGO(F, X) do { if (few) TG_LAUNCH((tg_adam_update<F, X, true, 1024>), c1 - c0 + extra_wg, 1, 1024, 512, stream, u); \
-                           else TG_LAUNCH((tg_adam_update<F, X, true>), c1 - c0 + extra_wg, 1, 256, 128, stream, u); } while (0)
-    if (L.full) { if (x16) TG_AUGO(true, true); else TG_AUGO(true, false); }
-    else { if (x16) TG_AUGO(false, true); else TG_AUGO(false, false); }
-#undef TG_AUGO
+    tg_with_update_flags(L.full, x16, [&](auto fl, auto xh) {
+        constexpr bool F = decltype(fl)::value, X = decltype(xh)::value;
+        if (few) TG_LAUNCH((tg_adam_update<F, X, true, 1024>), c1 - c0 + extra_wg, 1, 1024, 512, stream, u);
+        else TG_LAUNCH((tg_adam_update<F, X, true>), c1 - c0 + extra_wg, 1, 256, 128, stream, u);
+    });
     if (whole) tg_prof_mark(m, "tg_adam_update");
     return TG_OK;
 }
@@ -1205,47 +1259,32 @@ static int tg_launch_small(tg_mapper* m, float* hist_row) {
 
 template <class PR>
 static int tg_one_step(tg_mapper* m, float lr, float* hist_row) {
-    int rc;
-    if (m->L.smallc) {
-        const bool constrained = (m->cfg.mode == TG_MODE_CONSTRAINED);
-        if ((rc = tg_launch_small(m, hist_row))) return rc;
-        if (tg_launch_failed()) return tg_launch_status();
-        if ((rc = tg_launch_update(m, lr, !constrained, nullptr, 0, -1, true))) return rc;
-        if (m->L.full) {
-            tg_launch_hist_regs(m, m->stream, hist_row);
-            tg_prof_mark(m, "tg_hist_regs");
-        }
-        if (constrained) {
-            if ((rc = tg_launch_filter(m, true, lr, hist_row))) return rc;
-            if ((rc = tg_merge(m, m->fp(m->L.o_rowpair), 1, true, false))) return rc;
-        }
-        m->step += 1;
-        TG_LAUNCH_CK();
-        return TG_OK;
-    }
-    if ((rc = tg_launch_forward<PR>(m))) return rc;
-    if ((rc = tg_launch_ghat_stats(m))) return rc;
-    if ((rc = tg_launch_loss<PR>(m, hist_row))) return rc;
+    const TgLayout& L = m->L;
     const bool constrained = (m->cfg.mode == TG_MODE_CONSTRAINED);
-    if (m->L.V <= TG_ROWPASS_MAX_V) {
-        // a row of M and X fits the registers of one workgroup: the backward GEMM only stores X, the row dots are fused
-        // into the update (tg_adam_rowpass), which also leaves the regulariser row sums for tg_hist_regs / the filter
-        tg_launch_bwd<PR>(m, m->stream, 0, m->L.nct, true);
-        tg_prof_mark(m, "tg_bwd_kernel");
+    // a row of M and X fits the registers of one workgroup (clusters mode: always): X is all the kernels before the update leave, the
+    // row dots are fused into the update (tg_adam_rowpass), which also leaves the regulariser row sums for tg_hist_regs / the filter
+    const bool resident = L.V <= TG_ROWPASS_MAX_V;
+    int rc;
+    if (L.smallc) {
+        if ((rc = tg_launch_small(m, hist_row))) return rc;
+    } else {
+        if ((rc = tg_launch_forward<PR>(m))) return rc;
+        if ((rc = tg_launch_ghat_stats(m))) return rc;
+        if ((rc = tg_launch_loss<PR>(m, hist_row))) return rc;
+        if (resident) {
+            tg_launch_bwd<PR>(m, m->stream, 0, L.nct, true);
+            tg_prof_mark(m, "tg_bwd_kernel");
+        }
+    }
+    if (resident) {
         if (tg_launch_failed()) return tg_launch_status();       // stop at the first failed launch, named
         if ((rc = tg_launch_update(m, lr, !constrained, nullptr, 0, -1, true))) return rc;
-        if (m->L.full) {
-            tg_launch_hist_regs(m, m->stream, hist_row);
-            tg_prof_mark(m, "tg_hist_regs");
-        }
+        if (L.full) tg_hist_regs_marked(m, hist_row);
     } else {
         const bool deferred = m->fin_pending;
         if ((rc = tg_launch_rowdots<PR>(m, hist_row))) return rc;
         if ((rc = tg_launch_update(m, lr, !constrained))) return rc;
-        if (m->L.full && deferred) {
-            tg_launch_hist_regs(m, m->stream, hist_row);
-            tg_prof_mark(m, "tg_hist_regs");
-        }
+        if (L.full && deferred) tg_hist_regs_marked(m, hist_row);
     }
     if (constrained) {      // Adam on F, then fold the NEW filter into the forward row scale
         if ((rc = tg_launch_filter(m, true, lr, hist_row))) return rc;
@@ -1303,7 +1342,7 @@ static int tg_batch_groups(int n) { return n <= 3 ? n : std::min((int)TG_BATCH_M
 struct tg_batch {
     std::vector<tg_mapper*> h;
     unsigned char* dev;                              // caller-provided scratch: the argument arrays
-    size_t o_fwd, o_ghat, o_gene, o_emit, o_bwd, o_upd, o_hreg, o_filt, o_merge, o_scr, o_small, total;
+    size_t total;                                    // ... their bytes (tg_batch_arrays)
     std::vector<float*> hist;                        // history base pointers the argument arrays currently hold
     bool args_valid;
     // The argument arrays are assembled in page-locked host memory the batch owns and go to the device as ONE asynchronous copy:
@@ -1320,18 +1359,22 @@ struct tg_batch {
     tg_stream_t sub[TG_BATCH_MAX_GROUPS - 1];
     tg_event_t e_fork, e_join[TG_BATCH_MAX_GROUPS - 1];
 };
-static size_t tg_batch_layout(int n, tg_batch* b) {
+// The argument arrays of a batch of n mappings, one element per mapping, carved in this order from `base` at 256-byte boundaries: the
+// staging side (tg_batch_upload), the device side (tg_batch_step_impl) and, from a null base, the byte count.
+struct TgBatchArrays {
+    TgFwdArgs* fwd; TgGhatReduceArgs* ghat; TgGeneReduceArgs* gene; TgEmitArgs* emit; TgBwdArgs* bwd; TgUpdateArgs* upd;
+    TgHistRegArgs* hreg; TgFilterArgs* filt; TgMergeArgs* merge; float** scr; TgSmallArgs* small;
+    size_t bytes;
+};
+static TgBatchArrays tg_batch_arrays(unsigned char* base, int n) {
+    TgBatchArrays a;
     size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += rup(bytes, 256); return o; };
-    const size_t o_fwd = take(n * sizeof(TgFwdArgs)), o_ghat = take(n * sizeof(TgGhatReduceArgs)), o_gene = take(n * sizeof(TgGeneReduceArgs)),
-                 o_emit = take(n * sizeof(TgEmitArgs)), o_bwd = take(n * sizeof(TgBwdArgs)), o_upd = take(n * sizeof(TgUpdateArgs)),
-                 o_hreg = take(n * sizeof(TgHistRegArgs)), o_filt = take(n * sizeof(TgFilterArgs)), o_merge = take(n * sizeof(TgMergeArgs)),
-                 o_scr = take(n * sizeof(float*)), o_small = take(n * sizeof(TgSmallArgs));
-    if (b) { b->o_small = o_small; b->o_fwd = o_fwd; b->o_ghat = o_ghat; b->o_gene = o_gene; b->o_emit = o_emit; b->o_bwd = o_bwd; b->o_upd = o_upd; b->o_hreg = o_hreg;
-             b->o_filt = o_filt; b->o_merge = o_merge; b->o_scr = o_scr; b->total = off; }
-    return off;
+    auto take = [&](auto*& p) { p = (std::remove_reference_t<decltype(p)>)((uintptr_t)base + off); off += rup((size_t)n * sizeof *p, 256); };
+    take(a.fwd); take(a.ghat); take(a.gene); take(a.emit); take(a.bwd); take(a.upd); take(a.hreg); take(a.filt); take(a.merge); take(a.scr); take(a.small);
+    a.bytes = off;
+    return a;
 }
-extern "C" size_t tg_batch_query_bytes(int n_mappers) { return n_mappers > 0 ? tg_batch_layout(n_mappers, nullptr) : 0; }
+extern "C" size_t tg_batch_query_bytes(int n_mappers) { return n_mappers > 0 ? tg_batch_arrays(nullptr, n_mappers).bytes : 0; }
 
 extern "C" int tg_batch_create(tg_mapper* const* mappers, int n, void* scratch_dev, tg_batch** out) {
     if (!mappers || n < 1 || !scratch_dev || !out) return tg_fail(TG_ERR_INVALID, "null argument or empty batch");
@@ -1355,7 +1398,7 @@ extern "C" int tg_batch_create(tg_mapper* const* mappers, int n, void* scratch_d
     if (!b) return tg_fail(TG_ERR_INVALID, "out of host memory");
     b->h.assign(mappers, mappers + n);
     b->dev = (unsigned char*)scratch_dev;
-    tg_batch_layout(n, b);
+    b->total = tg_batch_query_bytes(n);
     b->args_valid = false;
     b->upload_pending = false;
     b->e_upload = tg_event_t();
@@ -1393,40 +1436,35 @@ static int tg_batch_upload(tg_batch* b, float* const* hist) {
                                      "with the same history pointers before capturing");
     if (b->upload_pending) { tg_event_host_wait(b->e_upload); b->upload_pending = false; }       // the staging area is about to be rewritten
     memset(b->stage, 0, b->total);
-    TgFwdArgs* fw = (TgFwdArgs*)(b->stage + b->o_fwd); TgGhatReduceArgs* gh = (TgGhatReduceArgs*)(b->stage + b->o_ghat);
-    TgGeneReduceArgs* gr = (TgGeneReduceArgs*)(b->stage + b->o_gene); TgEmitArgs* em = (TgEmitArgs*)(b->stage + b->o_emit);
-    TgBwdArgs* bw = (TgBwdArgs*)(b->stage + b->o_bwd); TgUpdateArgs* up = (TgUpdateArgs*)(b->stage + b->o_upd);
-    TgHistRegArgs* hr = (TgHistRegArgs*)(b->stage + b->o_hreg); TgFilterArgs* fl = (TgFilterArgs*)(b->stage + b->o_filt);
-    TgMergeArgs* mg = (TgMergeArgs*)(b->stage + b->o_merge); float** scr = (float**)(b->stage + b->o_scr);
-    TgSmallArgs* sm = (TgSmallArgs*)(b->stage + b->o_small);
+    const TgBatchArrays A = tg_batch_arrays(b->stage, n);
     const bool constrained = (b->h[0]->cfg.mode == TG_MODE_CONSTRAINED);
     for (int i = 0; i < n; ++i) {
         tg_mapper* m = b->h[i];
         const TgLayout& L = m->L;
         int grid;
-        fw[i] = tg_fwd_args<PR>(m, -1, nullptr, false, &grid);
-        gh[i] = tg_ghat_args(m, false);
-        gr[i] = TgGeneReduceArgs{m->fp(L.o_genepart), (L.V + TG_RB - 1) / TG_RB, L.Kp, m->fp(L.o_genestat)};
+        A.fwd[i] = tg_fwd_args<PR>(m, -1, nullptr, false, &grid);
+        A.ghat[i] = tg_ghat_args(m, false);
+        A.gene[i] = TgGeneReduceArgs{m->fp(L.o_genepart), (L.V + TG_RB - 1) / TG_RB, L.Kp, m->fp(L.o_genestat)};
         TgFinalizeArgs f;
-        tg_loss_args(m, nullptr, f, em[i]);
+        tg_loss_args(m, nullptr, f, A.emit[i]);
         f.hist = hist ? hist[i] : nullptr;                      // BASE of the mapping's history (row offset: TgStepVar)
-        em[i].fin = f;
-        bw[i] = tg_bwd_args<PR>(m, 0, L.nct, &grid);
+        A.emit[i].fin = f;
+        A.bwd[i] = tg_bwd_args<PR>(m, 0, L.nct, &grid);
         if (L.smallc) {                                             // clusters mode: tg_sc_forward / tg_sc_backward take the place of the GEMMs
-            sm[i] = tg_small_args(m, nullptr);
-            sm[i].fin.hist = f.hist;
-            f = sm[i].fin;                                          // (one block of per-spot statistics: nky = 1)
-            gr[i].nrb = tg_small_nblk(L);
+            A.small[i] = tg_small_args(m, nullptr);
+            A.small[i].fin.hist = f.hist;
+            f = A.small[i].fin;                                     // (one block of per-spot statistics: nky = 1)
+            A.gene[i].nrb = tg_small_nblk(L);
         }
-        up[i] = tg_update_args(m, 0.f, !constrained, 0, L.C);       // (MapperConstrained: tg_merge_stats folds the NEW filter in afterwards)
-        up[i].fin = f; up[i].fin_on = 1;
-        hr[i] = TgHistRegArgs{m->fp(L.o_rowq), L.C, hist ? hist[i] : nullptr, m->cfg.lambda_r, m->cfg.lambda_l1, m->cfg.lambda_l2, constrained ? 1 : 0};
+        A.upd[i] = tg_update_args(m, 0.f, !constrained, 0, L.C);    // (MapperConstrained: tg_merge_stats folds the NEW filter in afterwards)
+        A.upd[i].fin = f; A.upd[i].fin_on = 1;
+        A.hreg[i] = TgHistRegArgs{m->fp(L.o_rowq), L.C, hist ? hist[i] : nullptr, m->cfg.lambda_r, m->cfg.lambda_l1, m->cfg.lambda_l2, constrained ? 1 : 0};
         if (constrained) {
-            fl[i] = tg_filter_args(m, true, 0.f, nullptr);
-            fl[i].hist = hist ? hist[i] : nullptr;               // BASE of the history (row offset: TgStepVar), like the update kernel's
-            mg[i] = tg_merge_args(m, m->fp(L.o_rowpair), 1, true, false, nullptr, 0);
+            A.filt[i] = tg_filter_args(m, true, 0.f, nullptr);
+            A.filt[i].hist = hist ? hist[i] : nullptr;           // BASE of the history (row offset: TgStepVar), like the update kernel's
+            A.merge[i] = tg_merge_args(m, m->fp(L.o_rowpair), 1, true, false, nullptr, 0);
         }
-        scr[i] = m->fp(L.o_scal);
+        A.scr[i] = m->fp(L.o_scal);
     }
     TG_CK(tg_memcpy_h2d(b->dev, b->stage, b->total, s));          // one copy, asynchronous (page-locked source that outlives the call)
     tg_event_record(b->e_upload, s);
@@ -1435,20 +1473,6 @@ static int tg_batch_upload(tg_batch* b, float* const* hist) {
     for (int i = 0; i < n; ++i) b->hist[i] = hist ? hist[i] : nullptr;
     b->args_valid = true;
     return TG_OK;
-}
-
-template <bool FULL, bool X16>
-static void tg_launch_rowpass_b(const TgUpdateArgs* argv, TgStepVar var, int rows, int V, int nb, tg_stream_t stream) {
-#define TG_RPB(NQ, NT) TG_LAUNCH3((tg_adam_rowpass_b<FULL, X16, NQ, NT>), rows, 1, nb, NT, 256, stream, argv, var)
-    if (V <= 4096) {
-        const int nq = (V + 1023) / 1024;
-        if (nq <= 1) TG_RPB(1, 256); else if (nq <= 2) TG_RPB(2, 256); else TG_RPB(4, 256);
-    } else {
-        const int nq = (V + 2047) / 2048;
-        if (nq <= 3) TG_RPB(3, 512); else if (nq <= 4) TG_RPB(4, 512); else if (nq <= 5) TG_RPB(5, 512);
-        else if (nq <= 6) TG_RPB(6, 512); else TG_RPB(8, 512);
-    }
-#undef TG_RPB
 }
 
 template <class PR>
@@ -1465,14 +1489,7 @@ static int tg_batch_step_impl(tg_batch* b, int n_steps, float lr, float* const* 
     int gf, gb;
     (void)tg_fwd_args<PR>(m0, -1, nullptr, false, &gf);
     (void)tg_bwd_args<PR>(m0, 0, L.nct, &gb);
-    const TgFwdArgs* a_fwd0 = (const TgFwdArgs*)(b->dev + b->o_fwd);
-    const TgGhatReduceArgs* a_gh0 = (const TgGhatReduceArgs*)(b->dev + b->o_ghat);
-    const TgGeneReduceArgs* a_gr0 = (const TgGeneReduceArgs*)(b->dev + b->o_gene);
-    const TgEmitArgs* a_em0 = (const TgEmitArgs*)(b->dev + b->o_emit);
-    const TgBwdArgs* a_bw0 = (const TgBwdArgs*)(b->dev + b->o_bwd);
-    const TgUpdateArgs* a_up0 = (const TgUpdateArgs*)(b->dev + b->o_upd);
-    const TgHistRegArgs* a_hr0 = (const TgHistRegArgs*)(b->dev + b->o_hreg);
-    const TgSmallArgs* a_sm0 = (const TgSmallArgs*)(b->dev + b->o_small);
+    const TgBatchArrays A = tg_batch_arrays(b->dev, n);
     const int nblk = tg_small_nblk(L), sc_nch = (L.Kp + TG_SC_KC - 1) / TG_SC_KC;
     const bool want_vox = (m0->cfg.lambda_g2 != 0.f);
     const int NG = b->n_groups, n_all = n;
@@ -1484,39 +1501,49 @@ static int tg_batch_step_impl(tg_batch* b, int n_steps, float lr, float* const* 
       for (int grp = 0; grp < NG; ++grp) {
         const int z0 = (int)((long long)grp * n_all / NG), n = (int)((long long)(grp + 1) * n_all / NG) - z0;     // this group's mappings
         tg_stream_t s = grp == 0 ? m0->stream : b->sub[grp - 1];
-        const TgFwdArgs* a_fwd = a_fwd0 + z0; const TgGhatReduceArgs* a_gh = a_gh0 + z0; const TgGeneReduceArgs* a_gr = a_gr0 + z0;
-        const TgEmitArgs* a_em = a_em0 + z0; const TgBwdArgs* a_bw = a_bw0 + z0; const TgUpdateArgs* a_up = a_up0 + z0;
-        const TgHistRegArgs* a_hr = a_hr0 + z0; const TgSmallArgs* a_sm = a_sm0 + z0;
+        const TgUpdateArgs* a_up = A.upd + z0; const TgSmallArgs* a_sm = A.small + z0;
         if (L.smallc) {
 #define TG_SC_FWD_B(CM, VX) TG_LAUNCH3((tg_sc_forward_b<CM, VX>), nblk, sc_nch, n, TG_SC_KC, tg_sc_lds_fwd(), s, a_sm)
             TG_SC_DISPATCH(L.C, want_vox, TG_SC_FWD_B);
 #undef TG_SC_FWD_B
-            TG_LAUNCH3(tg_gene_reduce_b, (L.Kp + 63) / 64, 1, n, 1024, TG_GR_GROUPS * 64 * 2 * 4, s, a_gr);
+            TG_LAUNCH3(tg_gene_reduce_b, (L.Kp + 63) / 64, 1, n, 1024, TG_GR_GROUPS * 64 * 2 * 4, s, A.gene + z0);
 #define TG_SC_BWD_B(CM, VX) TG_LAUNCH3((tg_sc_backward_b<CM>), nblk, 1, n, TG_SC_KC, tg_sc_lds_bwd(), s, a_sm)
             TG_SC_DISPATCH(L.C, false, TG_SC_BWD_B);
 #undef TG_SC_BWD_B
         } else {
-        if (L.fwd_wide) {
-            if constexpr (PR::NP == 2) TG_LAUNCH3((tg_fwd_kernel_b<PR, TgGeoWide>), gf, 1, n, TgGeoWide::NT, TgGeoWide::LDS_BYTES, s, a_fwd);
-        } else if (L.T == 256) TG_LAUNCH3((tg_fwd_kernel_b<PR, TgGeoLarge>), gf, 1, n, TgGeoLarge::NT, TgGeoLarge::LDS_BYTES, s, a_fwd);
-        else TG_LAUNCH3((tg_fwd_kernel_b<PR, TgGeoSmall>), gf, 1, n, TgGeoSmall::NT, TgGeoSmall::LDS_BYTES, s, a_fwd);
-        TG_LAUNCH3(tg_ghat_reduce_b, nrb, (L.Kp + TG_GH_COLS - 1) / TG_GH_COLS, n, 256, 4 * 64 * 2 * 16, s, a_gh);
-        TG_LAUNCH3(tg_gene_reduce_b, (L.Kp + 63) / 64, 1, n, 1024, TG_GR_GROUPS * 64 * 2 * 4, s, a_gr);
-        TG_LAUNCH3((tg_dghat_emit_b<PR>), nrb, 1, n, 256, (2 * L.Kp + 2 * TG_RB) * 4, s, a_em);
-        if (L.T == 256) TG_LAUNCH3((tg_bwd_kernel_b<PR, TgGeoLarge>), gb, 1, n, TgGeoLarge::NT, TgGeoLarge::BWD_LDS_BYTES, s, a_bw);
-        else TG_LAUNCH3((tg_bwd_kernel_b<PR, TgGeoSmall>), gb, 1, n, TgGeoSmall::NT, TgGeoSmall::BWD_LDS_BYTES, s, a_bw);
+            tg_with_fwd_geo<PR>(L, [&](auto ge) {
+                using GE = typename decltype(ge)::type;
+                TG_LAUNCH3((tg_fwd_kernel_b<PR, GE>), gf, 1, n, GE::NT, GE::LDS_BYTES, s, A.fwd + z0);
+            });
+            TG_LAUNCH3(tg_ghat_reduce_b, nrb, (L.Kp + TG_GH_COLS - 1) / TG_GH_COLS, n, 256, 4 * 64 * 2 * 16, s, A.ghat + z0);
+            if (tg_gene_reduce_is_tall(nrb)) {      // no batched twin, and another order of the sums: the solo kernel, once per mapping
+                for (int i = z0; i < z0 + n; ++i)
+                    TG_LAUNCH(tg_gene_reduce_tall, (L.Kp + 15) / 16, 1, 1024, TG_GR_GROUPS * 64 * 2 * 4, s, (const float*)b->h[i]->fp(b->h[i]->L.o_genepart), nrb,
+                              L.Kp, b->h[i]->fp(b->h[i]->L.o_genestat));
+            } else TG_LAUNCH3(tg_gene_reduce_b, (L.Kp + 63) / 64, 1, n, 1024, TG_GR_GROUPS * 64 * 2 * 4, s, A.gene + z0);
+            TG_LAUNCH3((tg_dghat_emit_b<PR>), nrb, 1, n, 256, (2 * L.Kp + 2 * TG_RB) * 4, s, A.emit + z0);
+            // By the layout's tile edge L.T, like the arguments (tg_bwd_args with tile 0), not by L.bwd_T as tg_launch_bwd: a batch ignores
+            // a tg_config.bwd_tile of 128 under the 256 layout.  The automatic choice cannot differ: it needs the row-dot epilogue.
+            tg_with_tile_geo(L.T, [&](auto ge) {
+                using GE = typename decltype(ge)::type;
+                TG_LAUNCH3((tg_bwd_kernel_b<PR, GE>), gb, 1, n, GE::NT, GE::BWD_LDS_BYTES, s, A.bwd + z0);
+            });
         }
         const double t = (double)(m0->step + 1);
         TgStepVar var;
         var.step_size = (float)((double)lr / (1.0 - pow((double)m0->cfg.beta1, t)));
         var.bc2_sqrt = (float)sqrt(1.0 - pow((double)m0->cfg.beta2, t));
         var.hist_row = hist ? (long long)(first_row + it) : -1;
-        if (L.full) { if (x16) tg_launch_rowpass_b<true, true>(a_up, var, L.C + 1, L.V, n, s); else tg_launch_rowpass_b<true, false>(a_up, var, L.C + 1, L.V, n, s); }
-        else { if (x16) tg_launch_rowpass_b<false, true>(a_up, var, L.C + 1, L.V, n, s); else tg_launch_rowpass_b<false, false>(a_up, var, L.C + 1, L.V, n, s); }
-        if (L.full) TG_LAUNCH3(tg_hist_regs_b, 1, 1, n, 1024, 64, s, a_hr, var);
+        tg_with_update_flags(L.full, x16, [&](auto fl, auto xh) {      // (a batch never streams: tg_adam_rowpass_b)
+            tg_with_row_length(L.V, [&](auto nq, auto nt) {
+                constexpr int NQ = decltype(nq)::value, NT = decltype(nt)::value;
+                TG_LAUNCH3((tg_adam_rowpass_b<decltype(fl)::value, decltype(xh)::value, NQ, NT>), L.C + 1, 1, n, NT, 256, s, a_up, var);
+            });
+        });
+        if (L.full) TG_LAUNCH3(tg_hist_regs_b, 1, 1, n, 1024, 64, s, A.hreg + z0, var);
         if (m0->cfg.mode == TG_MODE_CONSTRAINED) {      // Adam on the filters, then the new filters folded into the forward row constants
-            TG_LAUNCH3(tg_filter_kernel_b, 1, 1, n, 1024, 64, s, (const TgFilterArgs*)(b->dev + b->o_filt) + z0, var, (float* const*)(b->dev + b->o_scr) + z0);
-            TG_LAUNCH3(tg_merge_stats_b, (L.C + 255) / 256, 1, n, 256, 0, s, (const TgMergeArgs*)(b->dev + b->o_merge) + z0);
+            TG_LAUNCH3(tg_filter_kernel_b, 1, 1, n, 1024, 64, s, A.filt + z0, var, A.scr + z0);
+            TG_LAUNCH3(tg_merge_stats_b, (L.C + 255) / 256, 1, n, 256, 0, s, A.merge + z0);
         }
       }
         for (int i = 0; i < n_all; ++i) b->h[i]->step += 1;
@@ -1536,12 +1563,9 @@ extern "C" int tg_batch_step(tg_batch* b, int n_steps, float lr, float* const* h
         if (b->h[i]->step != b->h[0]->step) return tg_fail(TG_ERR_STATE, "the mappers of the batch are at different steps (one was stepped on its own)");
         b->h[i]->fin_pending = false;
     }
-    switch (b->h[0]->cfg.precision) {
-        case TG_PREC_F32: return tg_batch_step_impl<PrecF32>(b, n_steps, lr, history_dev, first_row);
-        case TG_PREC_BF16: return tg_batch_step_impl<PrecBF16>(b, n_steps, lr, history_dev, first_row);
-        case TG_PREC_BF16X2S: return tg_batch_step_impl<PrecBF16x2S>(b, n_steps, lr, history_dev, first_row);
-        default: return tg_batch_step_impl<PrecBF16x3>(b, n_steps, lr, history_dev, first_row);
-    }
+    return tg_with_precision(b->h[0]->cfg.precision, [&](auto pr) {
+        return tg_batch_step_impl<typename decltype(pr)::type>(b, n_steps, lr, history_dev, first_row);
+    });
 }
 
 // ---- spot-sharded multi-GPU path --------------------------------------------------------------------------------------
@@ -1949,10 +1973,7 @@ static int tg_one_step_sharded(tg_mapper* m, float lr, float* hist_row) {
     if (!fused && (rc = tg_exchange_all_reduce(m, m->fp(L.o_rowq), (size_t)(L.full ? TGP1_N : 1) * L.C))) return rc;   // E3: row dots (+ regulariser row sums)
     if ((rc = tg_launch_update(m, lr, false, nullptr, 0, -1, false, fused ? &link : nullptr))) return rc;   // Adam; local (max, sum exp) [fused: pushed];
                                                                                                             // deferred history row by its extra workgroup
-    if (L.full) {                                               // the row sums are global now: every rank adds the same scalars
-        tg_launch_hist_regs(m, m->stream, hist_row);
-        tg_prof_mark(m, "tg_hist_regs");
-    }
+    if (L.full) tg_hist_regs_marked(m, hist_row);               // the row sums are global now: every rank adds the same scalars
     if (m->cfg.mode == TG_MODE_CONSTRAINED && (rc = tg_launch_filter(m, true, lr, hist_row))) return rc;   // replicated F: same result on every rank
     m->step += 1;
     if (fused) return tg_merge_fused(m, hist_row, link);        // E1 polled at the head of the merge
@@ -1960,28 +1981,12 @@ static int tg_one_step_sharded(tg_mapper* m, float lr, float* hist_row) {
 }
 
 static int tg_dispatch_step(tg_mapper* m, float lr, float* hist_row, bool prelaunched = false, bool prelaunch_next = false) {
-    if (m->comm) {
-        switch (m->cfg.precision) {
-            case TG_PREC_F32: return tg_one_step_sharded<PrecF32>(m, lr, hist_row);
-            case TG_PREC_BF16: return tg_one_step_sharded<PrecBF16>(m, lr, hist_row);
-            case TG_PREC_BF16X2S: return tg_one_step_sharded<PrecBF16x2S>(m, lr, hist_row);
-            default: return tg_one_step_sharded<PrecBF16x3>(m, lr, hist_row);
-        }
-    }
-    if (m->L.bands > 1 && !m->prof) {
-        switch (m->cfg.precision) {
-            case TG_PREC_F32: return tg_one_step_pipelined<PrecF32>(m, lr, hist_row, prelaunched, prelaunch_next);
-            case TG_PREC_BF16: return tg_one_step_pipelined<PrecBF16>(m, lr, hist_row, prelaunched, prelaunch_next);
-            case TG_PREC_BF16X2S: return tg_one_step_pipelined<PrecBF16x2S>(m, lr, hist_row, prelaunched, prelaunch_next);
-            default: return tg_one_step_pipelined<PrecBF16x3>(m, lr, hist_row, prelaunched, prelaunch_next);
-        }
-    }
-    switch (m->cfg.precision) {
-        case TG_PREC_F32: return tg_one_step<PrecF32>(m, lr, hist_row);
-        case TG_PREC_BF16: return tg_one_step<PrecBF16>(m, lr, hist_row);
-        case TG_PREC_BF16X2S: return tg_one_step<PrecBF16x2S>(m, lr, hist_row);
-        default: return tg_one_step<PrecBF16x3>(m, lr, hist_row);
-    }
+    return tg_with_precision(m->cfg.precision, [&](auto pr) {
+        using PR = typename decltype(pr)::type;
+        if (m->comm) return tg_one_step_sharded<PR>(m, lr, hist_row);
+        if (m->L.bands > 1 && !m->prof) return tg_one_step_pipelined<PR>(m, lr, hist_row, prelaunched, prelaunch_next);
+        return tg_one_step<PR>(m, lr, hist_row);
+    });
 }
 
 extern "C" int tg_mapper_step(tg_mapper* m, int n_steps, float lr, float* history_dev, int first_row) {
@@ -2019,13 +2024,7 @@ extern "C" int tg_mapper_project(tg_mapper* m, float* Ghat_out_dev) {
     if (!m || !m->ready) return tg_fail(TG_ERR_STATE, "mapper not ready");
     if (!Ghat_out_dev) return tg_fail(TG_ERR_INVALID, "Ghat_out is NULL");
     const TgLayout& L = m->L;
-    int rc;
-    switch (m->cfg.precision) {
-        case TG_PREC_F32: rc = tg_launch_forward<PrecF32>(m); break;
-        case TG_PREC_BF16: rc = tg_launch_forward<PrecBF16>(m); break;
-        case TG_PREC_BF16X2S: rc = tg_launch_forward<PrecBF16x2S>(m); break;
-        default: rc = tg_launch_forward<PrecBF16x3>(m); break;
-    }
+    int rc = tg_with_precision(m->cfg.precision, [&](auto pr) { return tg_launch_forward<typename decltype(pr)::type>(m); });
     if (rc) return rc;
     if ((rc = tg_launch_ghat_stats(m))) return rc;
     TG_CK(tg_memcpy2d(Ghat_out_dev, (size_t)L.K * 4, m->ws + L.o_Ghat, (size_t)L.Kp * 4, (size_t)L.K * 4, L.V, m->stream));
@@ -2057,12 +2056,9 @@ extern "C" int tg_mapper_project_genes(tg_mapper* m, const float* S_dev, int64_t
                   (const float*)m->fp(L.o_rinvz), L.C, m->fp(L.o_rowent));
     for (int k0 = 0; k0 < n_genes; k0 += L.K) {
         const int kc = (n_genes - k0 < L.K) ? n_genes - k0 : L.K;
-        int rc;
-        switch (m->cfg.precision) {
-            case TG_PREC_F32: rc = tg_project_block<PrecF32>(m, S_dev + k0, ld_s, kc, plain); break;
-            case TG_PREC_BF16: rc = tg_project_block<PrecBF16>(m, S_dev + k0, ld_s, kc, plain); break;
-            default: rc = tg_project_block<PrecBF16x3>(m, S_dev + k0, ld_s, kc, plain); break;
-        }
+        int rc = tg_with_precision(tg_project_genes_precision(m->cfg.precision), [&](auto pr) {
+            return tg_project_block<typename decltype(pr)::type>(m, S_dev + k0, ld_s, kc, plain);
+        });
         if (rc) return rc;
         if ((rc = tg_launch_ghat_stats(m))) return rc;
         TG_CK(tg_memcpy2d(out_dev + k0, (size_t)ld_out * 4, m->ws + L.o_Ghat, (size_t)L.Kp * 4, (size_t)kc * 4, L.V, m->stream));
@@ -2139,13 +2135,7 @@ extern "C" int tg_mapper_validate(tg_mapper* m, float* out4_dev) {
     const TgLayout& L = m->L;
     if (L.Vtot != L.V && !m->comm) return tg_fail(TG_ERR_STATE, "a spot shard needs tg_mapper_attach_comm before it can validate");
     if (m->cfg.mode != TG_MODE_MAPPER) return tg_fail(TG_ERR_INVALID, "MapperConstrained has no validation loss (mapping_optimizer.py:589)");
-    int rc;
-    switch (m->cfg.precision) {
-        case TG_PREC_F32: rc = tg_launch_forward<PrecF32>(m); break;
-        case TG_PREC_BF16: rc = tg_launch_forward<PrecBF16>(m); break;
-        case TG_PREC_BF16X2S: rc = tg_launch_forward<PrecBF16x2S>(m); break;
-        default: rc = tg_launch_forward<PrecBF16x3>(m); break;
-    }
+    int rc = tg_with_precision(m->cfg.precision, [&](auto pr) { return tg_launch_forward<typename decltype(pr)::type>(m); });
     if (rc) return rc;
     if ((rc = tg_launch_ghat_stats(m, true))) return rc;
     if (m->comm && (rc = tg_exchange_all_reduce(m, m->fp(L.o_genestat), (size_t)2 * L.Kp))) return rc;      // per-gene sums over all spots

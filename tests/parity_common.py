@@ -230,7 +230,8 @@ ROW_EPS_FRACTION = {"fp32": 0.05, "bf16x3": 0.05, "bf16": 0.2}
 
 
 def update_instantiation(C, V, precision, variant):
-    """The update kernel a single-GPU, more-than-32-cell handle launches (tg_launch_update / tg_launch_rowpass in tg_capi.hip):
+    """The update kernel a single-GPU, more-than-32-cell handle launches (tg_launch_update in tg_capi.hip: tg_with_update_flags
+    x tg_with_row_length):
     (kernel, FULL, X16, NQ, NT, STREAM); NQ is None for tg_adam_update."""
     full, x16 = variant != "plain", precision == "bf16"
     if V > 16384:                                       # backward with the row-dot epilogue, tg_rowsum_parts, tg_adam_update

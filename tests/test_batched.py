@@ -1,6 +1,8 @@
 """Batched independent mappings (tg_batch): B mappings of one shape advance in one launch per kernel
 (blockIdx.z = mapping).  CPU: through the emulated C ABI -- every batch element against the fp64 oracle and bit-identical to the
 same mapping trained on its own.  The GPU version of the same check is tests/test_gpu_parity.py::test_batched_mappings."""
+import contextlib
+
 import numpy as np
 import pytest
 
@@ -18,8 +20,28 @@ def sim():
     _capi._install_library_for_tests(None)
 
 
-def check_batched(device, precision, C, K, V, B, epochs, lam, tol_loss, tol_P):
-    """Leave-one-gene-out folds like cross_val (utils.py:576-600): fold i trains on all genes but gene i, own seed."""
+@contextlib.contextmanager
+def batches_taken():
+    """Sizes of the groups train_many really trained through one tg_batch: a group the C library refuses is trained on streams
+    without a word, and _train_batched only returns once the batch has run to the end."""
+    from tangram_amd import batched
+    taken, inner = [], batched._train_batched
+
+    def spy(mappers, *args, **kwargs):
+        out = inner(mappers, *args, **kwargs)
+        taken.append(len(mappers))
+        return out
+
+    batched._train_batched = spy
+    try:
+        yield taken
+    finally:
+        batched._train_batched = inner
+
+
+def check_batched(device, precision, C, K, V, B, epochs, lam, tol_loss, tol_P, batched="auto"):
+    """Leave-one-gene-out folds like cross_val (utils.py:576-600): fold i trains on all genes but gene i, own seed.
+    `batched=True`: the B folds must have gone through ONE tg_batch ("auto" may decline)."""
     import tangram_amd as tg
     import tangram_amd.mapping_optimizer as mo
     from oracle import tangram_oracle as orc
@@ -34,7 +56,9 @@ def check_batched(device, precision, C, K, V, B, epochs, lam, tol_loss, tol_P):
         kw, seed = fold(i)
         return lambda: mo.Mapper(device=device, random_state=seed, gemm_precision=precision, **kw)
 
-    res, mappers = tg.train_many([builder(i) for i in range(B)], epochs, 0.1, device=device)
+    with batches_taken() as taken:
+        res, mappers = tg.train_many([builder(i) for i in range(B)], epochs, 0.1, device=device, batched=batched)
+    assert batched == "auto" or taken == [B], taken
     solo = [builder(i)().train(num_epochs=epochs, learning_rate=0.1, print_each=None) for i in range(B)]
     for i in range(B):
         P, hist = res[i]
@@ -53,7 +77,7 @@ def check_batched(device, precision, C, K, V, B, epochs, lam, tol_loss, tol_P):
     assert len({m._engine.logits()[3] for m in mappers}) == 1
 
 
-def check_batched_constrained(device, precision, C, K, V, B, epochs, tol_loss, tol_P):
+def check_batched_constrained(device, precision, C, K, V, B, epochs, tol_loss, tol_P, batched="auto"):
     """B MapperConstrained folds in one tg_batch (cross_val passes any `mode`, utils.py:576-600): every batch element bit-identical
     to the same mapping trained alone, and against the fp64 oracle (mapping, filter, history incl. count / f_reg terms)."""
     import tangram_amd as tg
@@ -72,8 +96,10 @@ def check_batched_constrained(device, precision, C, K, V, B, epochs, tol_loss, t
         kw, seed = fold(i)
         return lambda: mo.MapperConstrained(device=device, random_state=seed, gemm_precision=precision, **kw)
 
-    res, mappers = tg.train_many([builder(i) for i in range(B)], epochs, 0.1, device=device)
-    assert len({_batch_key(m) for m in mappers}) == 1 and _batch_key(mappers[0]) is not None      # they DID share one tg_batch
+    with batches_taken() as taken:
+        res, mappers = tg.train_many([builder(i) for i in range(B)], epochs, 0.1, device=device, batched=batched)
+    assert len({_batch_key(m) for m in mappers}) == 1 and _batch_key(mappers[0]) is not None      # they could share one tg_batch
+    assert batched == "auto" or taken == [B], taken                                               # ... and did
     solo = [builder(i)().train(num_epochs=epochs, learning_rate=0.1, print_each=None) for i in range(B)]
     keys = ("total_loss", "main_loss", "vg_reg", "kl_reg", "entropy_reg", "count_reg", "lambda_f_reg")
     for i in range(B):
@@ -148,6 +174,15 @@ def test_batched_folds_in_groups_emulated(sim):
     offsets, 9 Mapper folds as 4 + 5 and 13 MapperConstrained folds as 4 + 4 + 5."""
     check_batched("cpu", "fp32", C=9, K=12, V=66, B=9, epochs=4, lam=dict(lambda_d=1, lambda_g1=1, lambda_g2=0.5), tol_loss=1e-5, tol_P=2e-5)
     check_batched_constrained("cpu", "fp32", C=40, K=16, V=50, B=13, epochs=3, tol_loss=1e-5, tol_P=2e-5)
+
+
+@pytest.mark.parametrize("V", [2049, 8193])
+def test_batched_row_lengths_emulated(sim, V):
+    """The batch's rungs of the row-length ladder (tg_with_row_length in tg_capi.hip: the ladder of the solo update, but it launches
+    tg_adam_rowpass_b): 4 quads x 256 threads and 5 x 512 -- the batched instantiation with a launch bound of its own -- on the GEMM
+    path (33 cells: one past the clusters-mode bound).  The GPU walks every rung: tests/test_gpu_parity.py::test_batched_row_lengths."""
+    check_batched("cpu", "fp32", C=33, K=8, V=V, B=2, epochs=2, lam=dict(lambda_d=1, lambda_g1=1, lambda_g2=0.5), tol_loss=1e-5, tol_P=2e-5,
+                  batched=True)
 
 
 def test_batch_rejects_mixed_shapes(sim):

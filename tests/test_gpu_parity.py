@@ -363,6 +363,28 @@ def test_batched_mappings(precision):
                       tol_loss=tol["loss"], tol_P=tol["P"])
 
 
+@pytest.mark.parametrize("V", [2049, 4097, 6145, 8193, 10241, 12289, 16384])
+def test_batched_row_lengths(V):
+    """The batch's rungs of the row-length ladder (tg_with_row_length in tg_capi.hip -- the solo update's ladder, but it launches
+    tg_adam_rowpass_b): one V per (NQ, NT) the batched shapes above do not reach, and the last capacity.  33 cells, one past the
+    clusters-mode bound, take the GEMM path; the plain problem in fp32 and the constrained one in bf16 cover FULL and X16.  Every fold
+    bit-identical to the fold trained alone and against the fp64 oracle, the batch forced and seen to be taken."""
+    from tests.test_batched import check_batched, check_batched_constrained
+    tol = pc.TOL["fp32"]
+    check_batched(DEV, "fp32", C=33, K=8, V=V, B=2, epochs=3, lam=dict(lambda_d=1, lambda_g1=1, lambda_g2=0.5),
+                  tol_loss=tol["loss"], tol_P=tol["P"], batched=True)
+    tol = pc.TOL["bf16"]
+    check_batched_constrained(DEV, "bf16", C=33, K=8, V=V, B=2, epochs=3, tol_loss=tol["loss"], tol_P=tol["P"], batched=True)
+
+
+def test_batched_row_lengths_clusters_mode():
+    """... and clusters mode (18 cells: tg_sc_forward_b / tg_sc_backward_b before the same update) on the 5-quad, 512-thread rung."""
+    from tests.test_batched import check_batched
+    tol = pc.TOL["fp32"]
+    check_batched(DEV, "fp32", C=18, K=8, V=8193, B=2, epochs=3, lam=dict(lambda_d=1, lambda_g1=1, lambda_g2=0.5),
+                  tol_loss=tol["loss"], tol_P=tol["P"], batched=True)
+
+
 def test_batched_tuning_seeds_with_val_each():
     """f-3, the reference's tuning caller (mapping_parameter_tuning.py:110-129): three seeds with val_each=1 in ONE tg_batch give the
     histories (all nine keys) and mappings of three solo runs bit for bit -- at the clusters-mode shape and on the GEMM kernels."""

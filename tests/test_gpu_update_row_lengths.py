@@ -3,7 +3,7 @@ oracle, every case checked by tests/parity_common.update_row_case (schedule, fir
 3 epochs of history, P and the second moment element-wise, the filter, the padding columns).  The CPU twin on the emulator, with a
 subset of this table, is tests/test_update_row_lengths.py; its docstring maps each V to the instantiation it selects.
 
-The table: every capacity of tg_launch_rowpass and the value one past it, the switch to the two-kernel path at 16 385 spots, for
+The table: every capacity of tg_with_row_length (tg_capi.hip) and the value one past it, the switch to the two-kernel path at 16 385 spots, for
 each precision (fp32, bf16x3, bf16 -- X16) and variant (plain, regularised, constrained -- FULL), with C cycling through 33 (one
 past the clusters-mode bound), 64 / 65 (tg_adam_update's 1 024- / 256-thread switch) and 300 (three cell tiles, the history
 workgroup behind the last), some cases on the 256 layout; and one case per branch of stream_once (C * Vp * 16 B > 192 MiB).

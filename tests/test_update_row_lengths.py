@@ -1,6 +1,7 @@
 """The update kernel at every row length on the cells-mode GEMM path, on the HIP emulator (CPU; the GPU run of the whole table is
 tests/test_gpu_update_row_lengths.py).  A single GPU and more than 32 cells take the GEMM kernels (tg_is_clusters_problem is false);
-which update kernel runs then depends on the number of spots V (tg_launch_update / tg_launch_rowpass in tangram_amd/csrc/tg_capi.hip):
+which update kernel runs then depends on the number of spots V (tg_launch_update in tangram_amd/csrc/tg_capi.hip; the ladder from V to
+(NQ, NT) is tg_with_row_length, shared with the batched tg_adam_rowpass_b, and (FULL, X16, STREAM) is tg_with_update_flags):
 
     V               kernel(s)                                                     instantiation
     <= 1024         tg_adam_rowpass                                               <FULL, X16, 1, 256, STREAM>
@@ -76,7 +77,7 @@ def _kinds(cases):
 
 
 def _all_kinds():
-    """Every instantiation tg_launch_rowpass / tg_launch_update can select for a single GPU with C > 32."""
+    """Every instantiation tg_launch_update (tg_with_update_flags x tg_with_row_length) can select for a single GPU with C > 32."""
     kinds = set()
     for full in (False, True):
         for x16 in (False, True):
