@@ -70,6 +70,36 @@ def cos_mean_and_grad(A, B, axis):
     return cos.mean(), g, cos
 
 
+def validation_metrics(M, S, G, dtype=np.float64):
+    """The four numbers of `Mapper._val_loss_fn` (mapping_optimizer.py:321-333, evaluated on the training split) for the logits M
+    [C, V], S [C, K], G [V, K]: (val_total_loss = gene score + spot score, val_gene_sim, val_sp_sparsity_weighted_sim, val_entropy).
+
+    Cosines are clamped like `cos_stats` (1e-8).  The entropy is taken from log-softmax, P * (z - log Z), never log(P): a row so
+    sharp that P underflows off its peak still gives a finite number.  `dtype`: float64 is the checker; float32 evaluates the same
+    formula at the precision of the library (the conditioning check of tests/parity_common.validation_case)."""
+    dt = np.dtype(dtype)
+    M = np.asarray(M).astype(dt)
+    S = np.asarray(S).astype(dt)
+    G = np.asarray(G).astype(dt)
+    z = M - M.max(axis=1, keepdims=True)
+    E = np.exp(z)
+    Z = E.sum(axis=1, keepdims=True)
+    P = E / Z
+    Ghat = P.T @ S                                                    # :324
+    dot, na, nb = cos_stats(Ghat, G, 0)
+    cos_gene = dot / (na * nb)
+    dot, na, nb = cos_stats(Ghat, G, 1)
+    gv, vg = cos_gene.mean(), (dot / (na * nb)).mean()                # :326-327
+    # :330-331: the reference's gene_sparsity is an integer count over an integer, i.e. a float32 tensor whatever dtype the mapper
+    # computes in, and so are the weight 1 - (1 - fraction) and the sum of the weights.  The weights are restated in float32; their
+    # sum is exact here (torch's float32 sum lands one float32 ulp beside it on the golden case, in an order NumPy does not have)
+    frac32 = (G != 0).sum(axis=0).astype(np.float32) / np.float32(G.shape[0])
+    nonzero = (np.float32(1) - (np.float32(1) - frac32)).astype(dt)
+    weighted = (cos_gene * nonzero / nonzero.sum()).sum()             # :331
+    entropy = -((P * (z - np.log(Z))).sum(axis=1) / dt.type(np.log(M.shape[1]))).mean()       # :333
+    return float(gv + vg), float(gv), float(weighted), float(entropy)
+
+
 def xlogy(x, y):
     out = np.zeros_like(x)
     nz = x != 0

@@ -45,6 +45,13 @@ OWN_SPREAD = 3.0
 MEASURED_SPREAD = []
 
 
+# The validation metrics of the golden case cells_val (check_against_golden): multiple of TOL[precision]["loss"] they are held to.
+# Measured on the emulator (bf16x3, 7 epochs): 1.4e-7, i.e. 1 x would hold there; the 20-epoch GPU runs of the case in fp32, bf16x3 and
+# plain bf16 (tests/test_gpu_parity.py) have not been measured since the figures are printed, so the factor stays where it was.  The
+# 1 x bound is what tests/test_validation_metrics.py and tests/test_gpu_validation_metrics.py hold every path to, after 0, 1 and 3 steps.
+VAL_GOLDEN_FACTOR = 10.0
+
+
 def load_golden(name):
     return np.load(os.path.join(GOLDEN, name + ".npz"))
 
@@ -145,7 +152,10 @@ def check_against_golden(res, precision, full_length, own_spread=None):
         for k in ("val_total_loss", "val_gene_sim", "val_sp_sparsity_weighted_sim", "val_entropy"):
             got = np.array(res["hist"][k], dtype=np.float64)
             ref = z["f64_hist_" + k][:len(got)]
-            assert len(got) > 0 and float(np.abs(got - ref).max()) <= 10 * tol["loss"], (k, got, ref)
+            assert len(got) > 0
+            err = float(np.abs(got - ref).max())
+            print(f"golden {res.get('name')} {precision} {k}: max |delta| over {len(got)} validations {err:.2e}")
+            assert err <= VAL_GOLDEN_FACTOR * tol["loss"], (k, got, ref)
     np.testing.assert_allclose(res["P"].sum(axis=1), 1.0, atol=1e-5)
     assert (res["P"] >= 0).all()
 
@@ -697,3 +707,277 @@ def spatial_determinism_case(device, precision, seed=7):
     b = _run_engine(device, precision, data, M0, lam, _engine_graphs(kw, True))
     np.testing.assert_array_equal(a[0], b[0])
     np.testing.assert_array_equal(a[1], b[1])
+
+
+# ---- the validation metrics of Mapper._val_loss_fn on every kernel path (tests/test_validation_metrics.py on the emulator,
+# tests/test_gpu_validation_metrics.py on the GPU) -------------------------------------------------------------------------------
+VAL_KEYS = ("val_total_loss", "val_gene_sim", "val_sp_sparsity_weighted_sim", "val_entropy")
+# Conditioning of a case's inputs, evaluated on the checker only: the fp64 formula evaluated in NumPy float32 stays within a third
+# of the tightest bound (TOL["fp32"]["loss"]) of its fp64 value at every point a case validates
+VAL_COND = TOL["fp32"]["loss"] / 3.0
+TG_RB, TG_GH_COLS, TG_SC_MAXC, ROWPASS_MAX_V = 16, 256, 32, 16384        # tg_kernels.h / tg_small.h / tg_capi.hip
+
+
+def val_nky(K, tile):
+    """Parts of voxstat: K + 1 gene columns padded to the tile (tg_make_layout), TG_GH_COLS columns per part (tg_ghat_reduce)."""
+    Kp = -(-(K + 1) // (tile or 128)) * (tile or 128)
+    return -(-Kp // TG_GH_COLS)
+
+
+def validation_problem(C, K, V, seed, zero_genes=0, sharpen=1.0):
+    """(S, G, d, M0) of one validation case.  zero_genes = z: the first z gene columns of G are zero in every spot, the next z in
+    every spot but one (their non-zero fraction is 0 and 1 / V); the rest stay as drawn.  sharpen: factor on the initial logits."""
+    from oracle import tangram_oracle as orc
+    data = orc.make_synthetic(C, K, V, seed=seed)
+    G = data["G"].copy()
+    if zero_genes:
+        z = int(zero_genes)
+        assert 2 * z < K, "at least one gene stays as drawn: the weighted score needs a non-zero weight"
+        G[:, :z] = 0.0
+        G[:, z:2 * z] = 0.0
+        G[np.arange(z) % V, np.arange(z, 2 * z)] = 3.0
+    M0 = (orc.reference_init_M(C, V, seed + 1) * np.float32(sharpen)).astype(np.float32)
+    return data["S"], G, data["d"], M0
+
+
+def _val_check(got, M, S, G, out, where):
+    """One validation of the library against the fp64 formula at logits M; keeps the largest errors in `out`."""
+    from oracle import tangram_oracle as orc
+    ref = orc.validation_metrics(M, S, G)
+    ref32 = orc.validation_metrics(M, S, G, dtype=np.float32)
+    assert all(np.isfinite(ref)), (where, ref)
+    for k, g, r, r32 in zip(VAL_KEYS, got, ref, ref32):
+        out["cond"] = max(out.get("cond", 0.0), abs(r32 - r))
+        out[k] = max(out.get(k, 0.0), abs(g - r) if np.isfinite(g) else np.inf)
+    out.setdefault("points", []).append((where, tuple(got), ref))
+    return ref
+
+
+def _val_assert(out, bound, label):
+    print(f"validation case {label}: " + " ".join(f"{k}={out[k]:.2e}" for k in VAL_KEYS + ("cond",)))
+    assert out["cond"] <= VAL_COND, f"inputs: the float32 evaluation of the checker is {out['cond']:.2e} from its float64 value (> {VAL_COND:.1e})"
+    for k in VAL_KEYS:
+        assert out[k] <= bound, f"{k}: |library - fp64 formula| = {out[k]:.3e} > {bound:.0e}   {out['points']}"
+
+
+def validation_case(device, C, K, V, precision, tile=0, lambda_g2=0.5, pipeline_bands=0, zero_genes=0, sharpen=1.0, s_exact=False,
+                    n=3, seed=0, label=""):
+    """engine.validate() before any step, after one step and after n steps against oracle.validation_metrics (fp64) at the
+    oracle's logits; returns the largest |difference| per metric.  Bound: TOL[precision]["loss"] absolute on each of the four
+    numbers (the fp32 row for a clusters-mode handle, whatever precision was asked).  The path is asserted: the small-C flag, the
+    tile and the bands of tg_debug_layout, the precision the handle reports, and (profile_read of the first step) the forward
+    kernel and the update kernels of update_instantiation.  A handle with bands > 1 is not profiled: profiling switches the
+    band pipeline off (tg_dispatch_step)."""
+    import ctypes as ct
+    from tangram_amd.engine import HipMapperEngine
+    from oracle import tangram_oracle as orc
+    S, G, d, M0 = validation_problem(C, K, V, seed, zero_genes, sharpen)
+    lam = dict(lambda_g1=1.0, lambda_d=1.0, lambda_g2=lambda_g2)
+    smallc = C <= TG_SC_MAXC and tile == 0 and V <= ROWPASS_MAX_V
+    o = orc.OracleMapper(S, G, d=d, M0=M0, dtype=np.float64, **lam)
+    e = HipMapperEngine(S, G, M0, d=d, device=device, precision=precision, lambdas=lam, tile_size=tile, pipeline_bands=pipeline_bands,
+                        s_exact="auto" if s_exact else False)
+    geo = (ct.c_int * 8)()
+    assert e._lib.tg_debug_layout(ct.byref(e.cfg), geo) == 0
+    assert (geo[7], geo[0], geo[6]) == (int(smallc), tile or 128, max(1, pipeline_bands)), f"smallc / tile / bands = {geo[7]}, {geo[0]}, {geo[6]}"
+    want = "fp32" if smallc else ("bf16x3 (S exact: 2 products)" if s_exact else precision)
+    assert e.effective_precision == want, (e.effective_precision, want)
+    bound = TOL["fp32" if smallc else precision]["loss"]
+    out = dict(kind=("tg_sc" if smallc else update_instantiation(C, V, precision, "plain")))
+    _val_check(e.validate(), o.M, S, G, out, "before any step")
+    hist = e.new_history(n)
+    if geo[6] == 1:
+        e.profile(True)
+        e.step(1, 0.1, hist, 0)
+        names = [k for k, _, _ in e.profile_read()]
+        e.profile(False)
+        if smallc:
+            assert "tg_sc_forward" in names and "tg_sc_backward" in names and "tg_fwd_kernel" not in names, names
+        else:
+            assert "tg_fwd_kernel" in names and "tg_sc_forward" not in names, names
+            if out["kind"][0] == "tg_adam_rowpass":
+                assert "tg_adam_rowpass" in names and "tg_adam_update" not in names and "tg_rowsum_parts" not in names, names
+            else:
+                assert "tg_rowsum_parts" in names and "tg_adam_update" in names and "tg_adam_rowpass" not in names, names
+        assert "tg_gene_reduce" in names, names
+    else:
+        e.step(1, 0.1, hist, 0)
+    o.step(0.1)
+    _val_check(e.validate(), o.M, S, G, out, "after 1 step")
+    e.step(n - 1, 0.1, hist, 1)
+    for _ in range(n - 1):
+        o.step(0.1)
+    _val_check(e.validate(), o.M, S, G, out, f"after {n} steps")
+    e.release()
+    _val_assert(out, bound, label or f"C{C} K{K} V{V} {precision}")
+    return out
+
+
+def validation_cases(gpu):
+    """The shared case table: dicts of id + the arguments of validation_case.  Every id names the edge it is there for.  The
+    emulated table keeps every edge and uses fewer cells where the edge does not need them.  Every case runs in bf16x3 (the
+    clusters-mode ones compute in fp32 whatever is asked); every third case of the GEMM path also in fp32 and in plain bf16; two
+    cases on the two-product path (s_exact: make_synthetic's S is count-valued)."""
+    Cs = 300 if gpu else 48                      # (GPU: three cell tiles where the edge is about genes)
+    base = []
+
+    def add(cid, C, K, V, **kw):
+        base.append(dict(id=cid, C=C, K=K, V=V, precision="bf16x3", **kw))
+
+    for V in (255, 256, 257, 513):               # tg_row_entropy: 256 threads stride over the spots of a row
+        add(f"spots-{V}-row-entropy-stride-256", 48, 20, V)
+    for V in (1023, 1024, 1025, 2050):           # tg_val_finalize: 1 024 threads stride over the spots
+        add(f"spots-{V}-finalize-stride-1024", 48, 20, V)
+    for K in (1023, 1024, 1025):                 # ... over the genes
+        add(f"genes-{K}-finalize-stride-1024", 40, K, 64)
+    for C in (1023, 1025):                       # ... over the row entropies
+        add(f"cells-{C}-finalize-stride-1024", C, 20, 64)
+    for tile in (128, 256):                      # voxstat parts of TG_GH_COLS = 256 gene columns, K + 1 padded to the tile
+        for K in (254, 255, 256, 300):
+            add(f"genes-{K}-tile{tile}-nky{val_nky(K, tile)}", Cs, K, 70, tile=tile)
+    add("genes-600-nky3", Cs, 600, 70)
+    add("lambda-g2-0-gemm-path", Cs, 20, 70, lambda_g2=0.0)
+    add("lambda-g2-0-clusters-path", 18, 20, 70, lambda_g2=0.0)
+    for V in (15, 16, 17, 33):                   # TG_RB = 16 spots per row block: gnnzpart / gfrac with genes that are zero (almost) everywhere
+        add(f"spots-{V}-row-block-of-16-sparse-genes", 40, 20, V, zero_genes=4)
+    add("spots-8200-tall-gene-reduce-sparse-genes", 40, 20, 8200, zero_genes=4)
+    add("spots-4000-after-rowpass-256-threads", 40, 8, 4000)                    # the row constants each update family leaves
+    add("spots-4100-after-rowpass-512-threads", 40, 8, 4100)
+    add("spots-16400-cells-40-after-adam-update-1024-threads", 40, 8, 16400)
+    add("spots-16400-cells-70-after-adam-update-256-threads", 70, 8, 16400)
+    add("clusters-1-cell", 1, 9, 70)
+    add("clusters-18-cells-250-genes-1300-spots", 18, 250, 1300)
+    add("clusters-32-cells-1300-spots", 32, 9, 1300)
+    add("clusters-32-cells-250-genes", 32, 250, 70)
+    add("cells-33-first-gemm-path", 33, 9, 70)
+    base.append(dict(id="clusters-18-cells-bf16-asked-fp32-runs", C=18, K=9, V=70, precision="bf16"))
+    add("clusters-18-cells-default-path", 18, 9, 70)
+    add("clusters-18-cells-tile128-pins-gemm-path", 18, 9, 70, tile=128)
+    for b in (2, 3):
+        add(f"pipeline-bands-{b}", 420, 16, 150, pipeline_bands=b)
+    for K in (6015, 6016, 6200):                 # Kp = 6 016 / 6 144 / 6 272 on 128 tiles: below, at and past the self-emit bound (6 128)
+        add(f"genes-{K}-all-genes-width", 40, K, 64)
+    if gpu:
+        # the 256-tile width of tests/test_gpu_wide_genes.py (K = 5 888: Kp = 6 144, the first off the self-emit path on 256 tiles) with
+        # the tile pinned on 300 cells: at that module's 4 200 x 5 888 x 1 500 the fp64 checker alone takes 15 s of CPU per case
+        add("genes-5888-all-genes-width-tile256", 300, 5888, 600, tile=256)
+    add("sharpened-logits-x30-spots-300", 48, 20, 300, sharpen=30.0)
+    out = list(base)
+    # (the emulator spends half a minute per handle of 8 200 or 16 400 spots: those cases run in bf16x3 alone there)
+    gemm = [c for c in base if not (c["C"] <= TG_SC_MAXC and not c.get("tile")) and c["K"] != 5888 and (gpu or c["V"] < 8000)]
+    for i, c in enumerate(gemm):
+        if i % 3 == 0:
+            out.append(dict(c, id=c["id"] + "-fp32", precision="fp32"))
+            out.append(dict(c, id=c["id"] + "-bf16", precision="bf16"))
+    for cid in ("spots-257-row-entropy-stride-256", "genes-256-tile128-nky2"):
+        c = [c for c in base if c["id"] == cid][0]
+        out.append(dict(c, id=cid + "-two-products", s_exact=True))
+    return out
+
+
+def run_validation_case(device, case):
+    kw = {k: v for k, v in case.items() if k != "id"}
+    return validation_case(device, seed=case["C"] + case["V"], label=case["id"], **kw)
+
+
+def _state_of(e):
+    M, m1, m2, step = e.logits()
+    return [x.cpu().numpy().copy() for x in (M, m1, m2)] + [step]
+
+
+def validation_undisturbed_case(device, C, K, V, precision="bf16x3", calls=(1, 1, 1, 1), **kw):
+    """A handle that validates (twice) after every call of `step` and a handle that never does: bit-identical history rows, logits
+    and both Adam moments, padding columns included; the two validations in a row return identical floats."""
+    from tangram_amd.engine import HipMapperEngine
+    S, G, d, M0 = validation_problem(C, K, V, C + V)
+    lam = dict(lambda_g1=1.0, lambda_d=1.0, lambda_g2=kw.pop("lambda_g2", 0.5))
+    res = []
+    for validate in (True, False):
+        e = HipMapperEngine(S, G, M0, d=d, device=device, precision=precision, lambdas=lam, **kw)
+        hist = e.new_history(sum(calls))
+        row = 0
+        if validate:
+            assert e.validate() == e.validate()
+        for k in calls:
+            e.step(k, 0.1, hist, row)
+            row += k
+            if validate:
+                a, b = e.validate(), e.validate()
+                assert a == b and all(np.isfinite(a)), (a, b)
+        res.append([hist.cpu().numpy().copy()] + _state_of(e))
+        e.release()
+    for name, x, y in zip(("history", "M", "exp_avg", "exp_avg_sq"), res[0], res[1]):
+        np.testing.assert_array_equal(x, y, err_msg=name)
+    assert res[0][4] == res[1][4] == sum(calls)
+
+
+def validation_refused_case(device):
+    """MapperConstrained has no validation loss: the handle refuses, with the library's message, and trains on."""
+    import pytest
+    from tangram_amd.engine import HipMapperEngine
+    from oracle import tangram_oracle as orc
+    C, K, V = 40, 12, 50
+    data = orc.make_synthetic(C, K, V, seed=5)
+    M0, F0 = orc.reference_init_MF_constrained(C, V, 6)
+    lam = dict(lambda_g1=1.0, lambda_d=1.0, lambda_g2=0.5, lambda_count=1.0, lambda_f_reg=1.0)
+    e = HipMapperEngine(data["S"], data["G"], M0, d=data["d"], F0=F0, mode="constrained", device=device, lambdas=lam, target_count=20.0)
+    hist = e.new_history(2)
+    e.step(1, 0.1, hist, 0)
+    with pytest.raises(Exception, match="MapperConstrained has no validation loss"):
+        e.validate()
+    e.step(1, 0.1, hist, 1)
+    assert np.isfinite(hist.cpu().numpy()[:, 0]).all()
+    e.release()
+
+
+def validation_shards_case(device, precision, world, C, K, V, empty_gene_on_rank=None, n=3, seed=13):
+    """Spot shards (threads, tests/local_comm.py) against the fp64 formula on the FULL problem: validate() before any step, after one
+    and after n steps; every rank returns the same floats; the history and this rank's state are bit-identical to a sharded run
+    that never validates.  empty_gene_on_rank = r: gene 0 is zero in every spot of rank r's block (its non-zero fraction comes
+    from the other ranks alone) and gene 1 is zero in every spot of every OTHER rank's block."""
+    from tangram_amd.sharded import make_sharded, shard_bounds
+    from oracle import tangram_oracle as orc
+    from tests.local_comm import run_ranks
+    S, G, d, M0 = validation_problem(C, K, V, seed)
+    if empty_gene_on_rank is not None:
+        lo, hi = shard_bounds(V, world, empty_gene_on_rank)
+        G[lo:hi, 0] = 0.0
+        G[:lo, 1] = 0.0
+        G[hi:, 1] = 0.0
+        G[lo, 1] = 2.0
+        assert G[:, 0].any() and G[:, 1].any()
+    lam = dict(lambda_g1=1.0, lambda_d=1.0, lambda_g2=0.5)
+
+    def rank_fn(comm, validate):
+        sh = make_sharded(S, G, M0, d=d, device=device, precision=precision, lambdas=lam, comm=comm)
+        hist = sh.eng.new_history(n)
+        vals = []
+        if validate:
+            vals.append(sh.validate())
+        sh.run(1, 0.1, hist, 0)
+        if validate:
+            vals.append(sh.validate())
+            assert sh.validate() == vals[-1]
+        sh.run(n - 1, 0.1, hist, 1)
+        if validate:
+            vals.append(sh.validate())
+        out = [hist.cpu().numpy().copy()] + _state_of(sh.eng) + [vals]
+        sh.release()
+        return out
+
+    with_val = run_ranks(world, lambda comm: rank_fn(comm, True))
+    without = run_ranks(world, lambda comm: rank_fn(comm, False))
+    o = orc.OracleMapper(S, G, d=d, M0=M0, dtype=np.float64, **lam)
+    bound = TOL[precision]["loss"]
+    out = {}
+    for i, steps in enumerate((0, 1, n)):
+        while o.t < steps:
+            o.step(0.1)
+        for r in range(world):
+            assert with_val[r][5][i] == with_val[0][5][i], f"rank {r} holds other numbers than rank 0 after {steps} steps"
+        _val_check(with_val[0][5][i], o.M, S, G, out, f"after {steps} steps")
+    for r in range(world):
+        for name, x, y in zip(("history", "M", "exp_avg", "exp_avg_sq", "step"), with_val[r], without[r]):
+            np.testing.assert_array_equal(x, y, err_msg=f"rank {r}: {name}")
+    _val_assert(out, bound, f"{world} shards C{C} K{K} V{V} {precision}" + (" (a gene empty on one shard)" if empty_gene_on_rank is not None else ""))
+    return out

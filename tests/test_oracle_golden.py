@@ -95,6 +95,40 @@ def test_trajectory_fp64(golden_dir, name):
         np.testing.assert_allclose(res[1], z["f64_F_out"], atol=1e-7)
 
 
+def test_validation_metrics_fp64(golden_dir):
+    """oracle.validation_metrics (the fp64 checker of tests/test_validation_metrics.py) against the reference's own _val_loss_fn
+    history: the golden case trained with val_each = 2, evaluated after the optimizer step of every even epoch
+    (mapping_optimizer.py:398-403), at the fp64 bound test_trajectory_fp64 holds that case to.
+
+    The sparsity-weighted score alone carries float32 in the reference's fp64 run: its weights (an integer count over an integer) and
+    their sum are float32 tensors, and torch's float32 sum of the 24 weights (7.7000003) is one float32 ulp from the exact sum of the
+    same float32 weights (7.6999999) -- a relative 6.2e-8 on the score, measured 5.1e-8 absolute.  That number is held to the same
+    2e-9 plus one float32 ulp of the weight sum, relative; the other three to 2e-9."""
+    name = "cells_val"
+    z = _load(golden_dir, name)
+    args, epochs, _ = build_inputs(name)
+    val_each = args.pop("val_each")
+    assert val_each == 2
+    m = orc.OracleMapper(M0=z["f32_M0"], dtype=np.float64, **args)
+    keys = ("val_total_loss", "val_gene_sim", "val_sp_sparsity_weighted_sim", "val_entropy")
+    got = {k: [] for k in keys}
+    for t in range(epochs):
+        m.step(0.1)
+        if t % val_each == 0:
+            for k, x in zip(keys, orc.validation_metrics(m.M, args["S"], args["G"])):
+                got[k].append(x)
+    grow = max(1.0, epochs / 50.0)
+    for k in keys:
+        ref = z["f64_hist_" + k]
+        assert len(ref) == len(got[k]) == (epochs + val_each - 1) // val_each
+        atol = 2e-9 * grow
+        if k == "val_sp_sparsity_weighted_sim":
+            wsum = np.float32(((args["G"] != 0).sum(axis=0) / args["G"].shape[0]).sum())
+            atol += float(np.spacing(wsum) / wsum) * float(np.abs(ref).max())
+            assert atol < 1.1e-7
+        np.testing.assert_allclose(np.array(got[k]), ref, rtol=0, atol=atol, err_msg=k)
+
+
 @pytest.mark.parametrize("name", NAMES)
 def test_trajectory_fp32_vs_reference_fp32(golden_dir, name):
     """Same-precision comparison: tolerance = the reference's own fp32-vs-fp64 spread."""
