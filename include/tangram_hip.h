@@ -217,6 +217,24 @@ int tg_mapper_attach_comm(tg_mapper* m, tg_comm* comm);
  * P_out_dev [C][V] dense, F_out_dev [C] (sigmoid(F)) or NULL.                                       */
 int tg_mapper_result(tg_mapper* m, float* P_out_dev, float* F_out_dev);
 
+/* Each cell's k most probable spots WITHOUT the dense mapping (what `np.argmax(adata_map.X, axis=1)` of count_cell_annotations,
+ * utils.py:257, per-cell placement and plots need): one streaming pass over the logits, each read once, that writes C x k pairs
+ * instead of the C x V plane of tg_mapper_result (1.2 GB at 30 000 x 10 000).  val_out_dev [C][k]: the k largest entries of the
+ * row of softmax(M) -- the very bits tg_mapper_result writes --, idx_out_dev [C][k]: their GLOBAL spot indices (cfg.spot_offset +
+ * column).  Order: value descending, equal values by ascending spot index (decided on the computed probabilities, not on the
+ * logits).  1 <= k <= 64 and k <= n_spots_total, else TG_ERR_INVALID.  A spot shard returns the best k of ITS spots; a shard with
+ * fewer than k spots fills the tail of each row with (0.0f, -1); tg_topk_merge combines the shards.  Constrained mode: softmax(M)
+ * without the filter, like adata_map.X (mapping_optimizer.py:637); the filter comes from tg_mapper_result, whose P_out_dev may be
+ * NULL when F_out_dev is given.  Asynchronous on the handle's stream; allocates nothing and writes nothing but the two outputs. */
+int tg_mapper_result_topk(tg_mapper* m, int32_t k, float* val_out_dev /*[C][k]*/, int32_t* idx_out_dev /*[C][k]*/);
+
+/* Merge per-row candidate lists val_in_dev / idx_in_dev [n_rows][ld_in] (first n_in columns) into the best k of each row under the
+ * order above -> val_out_dev / idx_out_dev [n_rows][k].  An index of -1 marks a pad: it sorts after every real entry, and rows
+ * with fewer than k real entries end in (0.0f, -1).  The real indices of a row must be pairwise different (the lists of the spot
+ * shards of one row are).  No handle: enqueued on `hip_stream`; allocates nothing.  1 <= k <= 64.                             */
+int tg_topk_merge(const float* val_in_dev, const int32_t* idx_in_dev, int64_t n_rows, int32_t n_in, int64_t ld_in,
+                  int32_t k, float* val_out_dev, int32_t* idx_out_dev, void* hip_stream);
+
 /* Replaces `adata_map.X.T @ S` (mapping_utils.py:402): Ghat_out_dev [V][K] = softmax(M)^T S (times f). */
 int tg_mapper_project(tg_mapper* m, float* Ghat_out_dev);
 

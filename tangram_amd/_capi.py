@@ -17,6 +17,8 @@ TG_ABI_VERSION = 6
 TG_MODE_MAPPER, TG_MODE_CONSTRAINED = 0, 1
 PRECISIONS = {"fp32": 0, "bf16": 1, "bf16x3": 2}
 H_NTERMS = 16
+TOPK_MAX = 64          # TG_TOPK_MAX / TG_TOPK_CHUNK of csrc/tg_topk.h (checked against tg_debug_topk_limits by the tests)
+TOPK_CHUNK = 8192
 H_TOTAL, H_MAIN, H_VG, H_KL, H_ENTROPY, H_L1, H_L2, H_NB, H_CT, H_COUNT, H_FREG, H_GETIS, H_MORAN, H_GEARY = range(14)
 
 
@@ -79,6 +81,9 @@ def _declare(lib):
     lib.tg_comm_destroy.restype = None
     lib.tg_mapper_attach_comm.argtypes = [vp, vp]
     lib.tg_mapper_result.argtypes = [vp, vp, vp]
+    lib.tg_mapper_result_topk.argtypes = [vp, ct.c_int32, vp, vp]
+    lib.tg_topk_merge.argtypes = [vp, vp, ct.c_int64, ct.c_int32, ct.c_int64, ct.c_int32, vp, vp, vp]
+    lib.tg_mapper_result_topk.restype = lib.tg_topk_merge.restype = i32
     lib.tg_mapper_project.argtypes = [vp, vp]
     lib.tg_mapper_project_genes.argtypes = [vp, vp, ct.c_int64, i32, vp, ct.c_int64, i32]
     lib.tg_csr_columns_to_dense.argtypes = [vp, vp, vp, ct.c_int64, i32, i32, vp, ct.c_int64, vp]
@@ -118,7 +123,7 @@ def _declare(lib):
 EXPORTS = ["tg_abi_version", "tg_last_error", "tg_query_sizes", "tg_mapper_create", "tg_mapper_destroy",
            "tg_mapper_step", "tg_comm_create_callbacks", "tg_comm_rccl_unique_id", "tg_comm_create_rccl", "tg_comm_peer_create", "tg_comm_peer_create_stepped", "tg_comm_peer_connect", "tg_comm_peer_status", "tg_comm_peer_set_timeout_ms",
            "tg_comm_all_reduce_sum", "tg_comm_all_gather", "tg_comm_destroy",
-           "tg_mapper_attach_comm", "tg_mapper_result",
+           "tg_mapper_attach_comm", "tg_mapper_result", "tg_mapper_result_topk", "tg_topk_merge",
            "tg_mapper_project", "tg_mapper_project_genes", "tg_csr_columns_to_dense", "tg_csr_gather_columns", "tg_row_sums",
            "tg_cluster_aggregate", "tg_batch_query_bytes", "tg_batch_create", "tg_batch_step", "tg_batch_destroy", "tg_mapper_state", "tg_mapper_set_step",
            "tg_mapper_filter_state", "tg_mapper_profile",

@@ -2008,14 +2008,42 @@ extern "C" int tg_mapper_step(tg_mapper* m, int n_steps, float lr, float* histor
 // ---- results ------------------------------------------------------------------------------------
 extern "C" int tg_mapper_result(tg_mapper* m, float* P_out_dev, float* F_out_dev) {
     if (!m || !m->ready) return tg_fail(TG_ERR_STATE, "mapper not ready");
-    if (!P_out_dev) return tg_fail(TG_ERR_INVALID, "P_out is NULL");
+    if (!P_out_dev && !F_out_dev) return tg_fail(TG_ERR_INVALID, "P_out is NULL");
     const TgLayout& L = m->L;
-    TG_LAUNCH(tg_softmax_out, L.C, 1, 256, 0, m->stream, (const float*)(m->st + L.s_M),
+    if (P_out_dev)            // (NULL with F_out given: the filter alone, for callers that take the mapping from tg_mapper_result_topk)
+        TG_LAUNCH(tg_softmax_out, L.C, 1, 256, 0, m->stream, (const float*)(m->st + L.s_M),
               (const float*)m->fp(L.o_rshift), (const float*)m->fp(L.o_rinvz), L.C, L.V, L.Vp, P_out_dev);
     if (F_out_dev) {
         if (m->cfg.mode != TG_MODE_CONSTRAINED) return tg_fail(TG_ERR_INVALID, "F_out requested from an unconstrained mapper");
         TG_CK(tg_memcpy(F_out_dev, m->ws + L.o_fgate, (size_t)L.C * 4, m->stream));
     }
+    TG_LAUNCH_CK();
+    return TG_OK;
+}
+
+// Each cell's k most probable spots of this handle's block of spots, from the logits: no dense plane is written (tg_topk.h).
+extern "C" int tg_mapper_result_topk(tg_mapper* m, int32_t k, float* val_out_dev, int32_t* idx_out_dev) {
+    if (!m || !m->ready) return tg_fail(TG_ERR_STATE, "mapper not ready");
+    const TgLayout& L = m->L;
+    if (k < 1 || k > TG_TOPK_MAX) return tg_fail(TG_ERR_INVALID, "top-k: k = %d is outside [1, %d]", k, TG_TOPK_MAX);
+    if (k > L.Vtot) return tg_fail(TG_ERR_INVALID, "top-k: k = %d exceeds the %d spots of the problem", k, L.Vtot);
+    if (!val_out_dev || !idx_out_dev) return tg_fail(TG_ERR_INVALID, "top-k: an output is NULL");
+    TgTopkArgs a;
+    a.M = (const float*)(m->st + L.s_M); a.rshift = m->fp(L.o_rshift); a.rinvz = m->fp(L.o_rinvz);
+    a.V = L.V; a.Vp = L.Vp; a.k = k; a.spot_offset = m->cfg.spot_offset; a.val = val_out_dev; a.idx = idx_out_dev;
+    TG_LAUNCH(tg_row_topk, L.C, 1, 256, TG_TOPK_LDS, m->stream, a);
+    TG_LAUNCH_CK();
+    return TG_OK;
+}
+
+extern "C" int tg_topk_merge(const float* val_in_dev, const int32_t* idx_in_dev, int64_t n_rows, int32_t n_in, int64_t ld_in, int32_t k,
+                             float* val_out_dev, int32_t* idx_out_dev, void* hip_stream) {
+    if (k < 1 || k > TG_TOPK_MAX) return tg_fail(TG_ERR_INVALID, "top-k merge: k = %d is outside [1, %d]", k, TG_TOPK_MAX);
+    if (!val_in_dev || !idx_in_dev || !val_out_dev || !idx_out_dev) return tg_fail(TG_ERR_INVALID, "top-k merge: null argument");
+    if (n_rows < 1 || n_rows > 0x7fffffffLL || n_in < 1 || ld_in < n_in)
+        return tg_fail(TG_ERR_INVALID, "top-k merge: bad lists: rows %lld, entries %d, pitch %lld", (long long)n_rows, n_in, (long long)ld_in);
+    TG_LAUNCH(tg_topk_merge_rows, n_rows, 1, 256, TG_TOPK_LDS, (tg_stream_t)hip_stream, val_in_dev, (const int*)idx_in_dev, n_in, (long long)ld_in,
+              k, val_out_dev, (int*)idx_out_dev);
     TG_LAUNCH_CK();
     return TG_OK;
 }
@@ -2286,6 +2314,11 @@ extern "C" int tg_debug_fwd_cover(const tg_config* cfg, long long* out) {
                 if ((slot[((size_t)vt * nkt + kt) * L.nsplit + i] != 0) != (i < tg_fwd_nseg(vt, nsteps, G, units))) bad = "partial slots are not 0 .. nseg - 1";
     if (bad) return tg_fail(TG_ERR_INVALID, "tg_debug_fwd_cover: %s (nvt %d nkt %d nsteps %d units %d)", bad, nvt, nkt, nsteps, units);
     out[0] = grid; out[1] = working; out[2] = lo; out[3] = hi; out[4] = most_seg; out[5] = L.nsplit;
+    return TG_OK;
+}
+// the compile-time limits of tg_topk.h: out[0] = largest k, out[1] = spots per chunk of tg_row_topk
+extern "C" int tg_debug_topk_limits(int32_t out[2]) {
+    out[0] = TG_TOPK_MAX; out[1] = TG_TOPK_CHUNK;
     return TG_OK;
 }
 // TEST HOOK: Adam's square root and divisions as the update kernels evaluate them (tg_device.h: tg_sqrt_cr, tg_div_fr, tg_div_by):

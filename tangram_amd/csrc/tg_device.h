@@ -83,6 +83,8 @@ TG_DEV void tg_glds16(const unsigned char* src, unsigned char* lds_wave_base) {
 TG_DEV void tg_glds16_uncounted(const unsigned char* src, unsigned char* lds_wave_base) { tg_glds16(src, lds_wave_base); }
 TG_DEV void tg_dma_drain() {}
 TG_DEV void tg_flag_or(int* p, int v) { *p |= v; }
+// atomic add on a counter in LDS, returns the old value (one fiber runs at a time: a plain add)
+TG_DEV int tg_lds_atomic_add(int* p, int v) { const int old = *p; *p = old + v; return old; }
 // buffer-descriptor form of the copy (see the HIP build below): descriptor = {base pointer, byte count}
 struct TgRsrc { const unsigned char* base; unsigned bytes; };
 TG_DEV TgRsrc tg_make_rsrc(const unsigned char* base, size_t bytes) { return TgRsrc{base, (unsigned)bytes}; }
@@ -194,6 +196,8 @@ TG_DEV void tg_glds16_uncounted(const unsigned char* src, unsigned char* lds_wav
 // and the next write to one of their registers then gets a vmcnt(0) of its own in the middle of the MFMA stream).
 TG_DEV void tg_dma_drain() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 TG_DEV void tg_flag_or(int* p, int v) { atomicOr(p, v); }
+// atomic add on a counter in LDS, returns the old value (ds_add_rtn_u32)
+TG_DEV int tg_lds_atomic_add(int* p, int v) { return atomicAdd(p, v); }
 // The copy through a BUFFER DESCRIPTOR: buffer_load_dwordx4 ... offen lds.  Source = descriptor base (SGPRs) + this lane's byte
 // offset (one VGPR, fixed for the whole tile) + soffset (an SGPR: the contraction step).  Against the global_load_lds form (64-bit
 // lane addresses rebuilt by two VALU instructions per copy and step) the loop carries no address arithmetic at all, and the copy

@@ -229,6 +229,37 @@ class HipMapperEngine:
         self._call(self._lib.tg_mapper_result, self._h, P.data_ptr(), F.data_ptr() if with_filter else None, tensors=(P, F))
         return (P, F) if with_filter else P
 
+    def filter_values(self):
+        """Constrained mode: sigmoid(F) [C] alone (tg_mapper_result without its dense plane)."""
+        F = torch.empty((self.C,), dtype=torch.float32, device=self.device)
+        self._call(self._lib.tg_mapper_result, self._h, None, F.data_ptr(), tensors=(F,))
+        return F
+
+    def result_topk(self, k):
+        """Each cell's k most probable spots of this handle's spots: (values [C, k] float32, indices [C, k] int32) device tensors,
+        value descending, equal values by ascending spot; the values are the bits `result()` holds at those places, the indices are
+        global (spot_offset + column); rows of a shard with fewer than k spots end in (0, -1).  One pass over the logits
+        (tg_mapper_result_topk): no C x V plane is written.  Constrained mode: softmax(M) without the filter, like adata_map.X."""
+        k = int(k)
+        val = torch.empty((self.C, max(k, 1)), dtype=torch.float32, device=self.device)
+        idx = torch.empty((self.C, max(k, 1)), dtype=torch.int32, device=self.device)
+        self._call(self._lib.tg_mapper_result_topk, self._h, k, val.data_ptr(), idx.data_ptr(), tensors=(val, idx))
+        return val, idx
+
+    def topk_merge(self, val, idx, k):
+        """Best k of every row of the candidate lists val / idx [n_rows, n_in] (index -1 = pad), same order (tg_topk_merge)."""
+        val = val.to(device=self.device, dtype=torch.float32)
+        idx = idx.to(device=self.device, dtype=torch.int32)
+        if val.dim() != 2 or val.shape != idx.shape or val.stride(1) != 1 or idx.stride(1) != 1 or val.stride(0) != idx.stride(0):
+            val, idx = val.contiguous(), idx.contiguous()
+        n_rows, n_in = val.shape
+        k = int(k)
+        out_v = torch.empty((n_rows, max(k, 1)), dtype=torch.float32, device=self.device)
+        out_i = torch.empty((n_rows, max(k, 1)), dtype=torch.int32, device=self.device)
+        self._call(self._lib.tg_topk_merge, val.data_ptr(), idx.data_ptr(), n_rows, n_in, int(val.stride(0)), k, out_v.data_ptr(),
+                   out_i.data_ptr(), self._hip_stream, tensors=(val, idx, out_v, out_i))
+        return out_v, out_i
+
     def project(self):
         Gh = torch.empty((self.V, self.K), dtype=torch.float32, device=self.device)
         self._call(self._lib.tg_mapper_project, self._h, Gh.data_ptr(), tensors=(Gh,))

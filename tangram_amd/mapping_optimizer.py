@@ -106,6 +106,28 @@ def _shared_seed(group, device):
     return int(t.item())
 
 
+def _topk_csr(values, indices, n_spots):
+    """The k (value, spot) pairs per cell as a canonical scipy CSR matrix [C, n_spots] (columns sorted inside a row; pads of
+    index -1 dropped)."""
+    import scipy.sparse as sp
+    values, indices = np.asarray(values, dtype=np.float32), np.asarray(indices, dtype=np.int64)
+    order = np.argsort(np.where(indices < 0, n_spots, indices), axis=1, kind="stable")
+    indices, values = np.take_along_axis(indices, order, 1), np.take_along_axis(values, order, 1)
+    real = indices >= 0
+    indptr = np.concatenate([[0], np.cumsum(real.sum(axis=1))]).astype(np.int64)
+    return sp.csr_matrix((values[real], indices[real].astype(np.int32), indptr), shape=(values.shape[0], int(n_spots)))
+
+
+def _result_topk(mapper, k):
+    """NumPy (values [C, k], indices [C, k]) of a trained mapper; a sharded mapper merges its ranks (collective)."""
+    val, idx = (mapper._sharded or mapper._engine).result_topk(k)
+    return val.detach().cpu().numpy(), idx.detach().cpu().numpy()
+
+
+def _n_spots_total(mapper):
+    return int(mapper._sharded.n_spots_total) if mapper._sharded is not None else int(mapper._engine.V)
+
+
 def _print_terms(names_vals):
     msg = ["{}: {:.3f}".format(k, v) for k, v in names_vals if not np.isnan(v)]
     print(str(msg).replace("[", "").replace("]", "").replace("'", ""))        # reference :307
@@ -243,8 +265,18 @@ class Mapper:
             out["entropy_reg"].append(float(row[_capi.H_ENTROPY]) if self.lambda_r else nan)
         return out
 
-    def train(self, num_epochs, learning_rate=0.1, print_each=100, val_each=None):
-        """Run the optimizer; returns (mapping matrix ndarray [C, V], training_history) like the reference (:358-408)."""
+    def result_topk(self, k):
+        """Each cell's k most probable spots of the current mapping: NumPy (values [C, k] float32, indices [C, k] int32), value
+        descending, equal values by ascending spot; 1 <= k <= 64.  The values are the entries of the mapping matrix at those
+        places; the dense C x V matrix is never formed (one pass over the logits on the device, C x k pairs come to the host).
+        On a sharded run: collective, every rank gets the same global result."""
+        return _result_topk(self, k)
+
+    def train(self, num_epochs, learning_rate=0.1, print_each=100, val_each=None, *, top_k=None):
+        """Run the optimizer; returns (mapping matrix ndarray [C, V], training_history) like the reference (:358-408).
+        top_k=k (1 .. 64): the mapping comes back as a canonical scipy.sparse.csr_matrix [C, V_total] that holds each cell's k
+        largest entries (`result_topk`) -- the dense matrix is neither written on the device nor copied to the host; `gather_result`
+        is ignored."""
         if self.random_state:
             torch.manual_seed(seed=self.random_state)        # reference :371-372 (no RNG is consumed afterwards)
         if print_each:
@@ -271,7 +303,9 @@ class Mapper:
                 _print_terms([(name, float(row[col])) for name, col in _PRINT_NAMES])
             if val_each is not None and (t - 1) % val_each == 0:
                 val_rows.append((self._sharded or eng).validate())   # reference :398-403: after optimizer.step() of epoch t-1
-        if self._sharded is not None and not self._gather_result:
+        if top_k is not None:
+            output = _topk_csr(*_result_topk(self, top_k), _n_spots_total(self))
+        elif self._sharded is not None and not self._gather_result:
             P_local, self.spot_range = self._sharded.result_local()      # this rank's spots only (gather_result=False)
             output = P_local.detach().cpu().numpy()
         elif self._sharded is not None:
@@ -382,10 +416,14 @@ class MapperConstrained:
                                            precision=gemm_precision, lambdas=lambdas, target_count=float(self.target_count),
                                            s_exact=s_exact)
 
-    def train(self, num_epochs, learning_rate=0.1, print_each=100):
+    def result_topk(self, k):
+        """Like Mapper.result_topk, of softmax(M) WITHOUT the filter -- what `adata_map.X` holds (:637)."""
+        return _result_topk(self, k)
+
+    def train(self, num_epochs, learning_rate=0.1, print_each=100, *, top_k=None):
         """Returns (mapping matrix [C, V], filter [C], training_history) like the reference (:589-639).
         History values are strings like the reference's (`str(x)`, :630); `total_loss` is `str(float)` rather than
-        the reference's tensor repr."""
+        the reference's tensor repr.  top_k: as for `Mapper.train` (the filter comes back whole)."""
         if self.random_state:
             torch.manual_seed(seed=self.random_state)
         eng = self._engine
@@ -405,6 +443,9 @@ class MapperConstrained:
                     self._sharded.checked()
                 row = hist[t - 1].detach().cpu().numpy()
                 _print_terms([(name, float(row[col])) for name, col in _PRINT_NAMES_CONSTRAINED])
+        if top_k is not None:
+            P = _topk_csr(*_result_topk(self, top_k), _n_spots_total(self))
+            return P, eng.filter_values().detach().cpu().numpy(), self._history_dict(hist[:num_epochs])
         if self._sharded is not None and not self._gather_result:
             P, self.spot_range, F = self._sharded.result_local(with_filter=True)
         elif self._sharded is not None:

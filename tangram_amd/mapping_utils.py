@@ -156,6 +156,7 @@ def map_cells_to_space(
     group=None,
     s_exact="auto",
     init="reference",
+    top_k=None,
 ):
     """Map single cell data (`adata_sc`) on spatial data (`adata_sp`); see the reference docstring (:169-203).
 
@@ -167,7 +168,11 @@ def map_cells_to_space(
     result (tangram_amd.mapping_optimizer); `keep_mapper=True` leaves the trained mapper on the
     result as `adata_map._tangram_amd_mapper` so that `tangram_amd.project_genes(..., mapper=adata_map._tangram_amd_mapper)`
     can project with the mapping still resident in HBM.  Default False: like the reference, the result owns no device
-    memory -- the logits, both Adam moments, X and the workspace (>= 16 bytes per cell x spot) are released before returning."""
+    memory -- the logits, both Adam moments, X and the workspace (>= 16 bytes per cell x spot) are released before returning.
+    `top_k=k` (opt-in, 1 .. 64): `adata_map.X` is a scipy CSR matrix with each cell's k most probable spots instead of the dense
+    cells x spots array (never written, never copied to the host), `adata_map.obs["top_k_mass"]` the share of each cell's mapping
+    those k entries hold, `adata_map.uns["top_k"] = k`; the training scores and the history are those of the dense call.
+    `project_genes` on such a result needs `mapper=` (keep_mapper=True)."""
     # ---- argument checks, reference :205-229
     if lambda_g1 == 0:
         raise ValueError("lambda_g1 cannot be 0.")
@@ -233,6 +238,7 @@ def map_cells_to_space(
 
     device = torch.device(device)                                             # :310
     print_each = 100 if verbose else None                                     # :312-315
+    topk_kw = {} if top_k is None else {"top_k": int(top_k)}
 
     if mode in ["cells", "clusters"]:
         voxel_weights, neighborhood_filter, ct_encode, spatial_weights = None, None, None, None      # :318-329
@@ -260,7 +266,7 @@ def map_cells_to_space(
         mapper = mo.Mapper(S=S, G=G, d=d, device=device, random_state=random_state, gemm_precision=gemm_precision,
                            distributed=distributed, group=group, s_exact=s_exact, init=init, **hyperparameters)   # :355-357
         mapping_matrix, training_history = mapper.train(
-            learning_rate=learning_rate, num_epochs=num_epochs, print_each=print_each)   # :361-363
+            learning_rate=learning_rate, num_epochs=num_epochs, print_each=print_each, **topk_kw)   # :361-363
     else:
         hyperparameters = {                                                   # :367-375
             "lambda_d": lambda_d, "lambda_g1": lambda_g1, "lambda_g2": lambda_g2, "lambda_r": lambda_r,
@@ -272,12 +278,15 @@ def map_cells_to_space(
                                       gemm_precision=gemm_precision, distributed=distributed, group=group, s_exact=s_exact, init=init,
                                       **hyperparameters)                      # :383-385
         mapping_matrix, F_out, training_history = mapper.train(
-            learning_rate=learning_rate, num_epochs=num_epochs, print_each=print_each)   # :387-389
+            learning_rate=learning_rate, num_epochs=num_epochs, print_each=print_each, **topk_kw)   # :387-389
 
     logging.info("Saving results..")
     adata_map = make_result_anndata(mapping_matrix, sc_view.obs.copy(), sp_view.obs.copy())   # :392-396
     if mode == "constrained":
         adata_map.obs["F_out"] = F_out                                        # :398-399
+    if top_k is not None:
+        adata_map.obs["top_k_mass"] = np.asarray(mapping_matrix.astype(np.float64).sum(axis=1)).reshape(-1)
+        adata_map.uns["top_k"] = int(top_k)
 
     # ---- per-gene training score, :401-410 (projection evaluated on the GPU; constrained: unfiltered like :402)
     if mode == "constrained":

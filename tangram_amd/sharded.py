@@ -407,6 +407,21 @@ class ShardedMapperEngine:
             F = F.detach().cpu().numpy()
         return (P, F) if with_filter else P
 
+    def result_topk(self, k):
+        """Each cell's k most probable spots over ALL spots (collective): (values [C, k] float32, indices [C, k] int32) device
+        tensors, identical on every rank -- every rank takes the best k of its own block (tg_mapper_result_topk: global indices,
+        (0, -1) behind the last spot of a block narrower than k), the C x k lists are gathered once (the values travel bit-cast
+        to int32 beside the indices) and merged on the device (tg_topk_merge).  No rank ever holds more than its own logits."""
+        k = int(k)
+        self.peer_check()
+        val, idx = self.eng.result_topk(k)
+        mine = torch.stack([val.view(torch.int32), idx]).contiguous()                 # [2, C, k]
+        outs = [torch.empty_like(mine) for _ in range(self.world)]
+        self.pycomm.all_gather(outs, mine)
+        both = torch.stack(outs, dim=2)                                                 # [2, C, world, k]: a row's lists side by side
+        C = val.shape[0]
+        return self.eng.topk_merge(both[0].reshape(C, self.world * k).view(torch.float32), both[1].reshape(C, self.world * k), k)
+
     def _gather_columns_host(self, X_local):
         bounds = [shard_bounds(self.n_spots_total, self.world, r, self.spatial) for r in range(self.world)]
         if not hasattr(self.pycomm, "broadcast"):

@@ -67,7 +67,7 @@ def project_genes(adata_map, adata_sc, cluster_label=None, scale=True, *, mapper
     may have been edited or filtered since training): `adata_map.X` is uploaded once and multiplied on the device.
     Extra keywords: `mapper` -- pass the trained `Mapper`/`MapperConstrained` EXPLICITLY (e.g. the
     `adata_map._tangram_amd_mapper` of `map_cells_to_space(..., keep_mapper=True)`) to project with the mapping that is
-    still resident in HBM instead; `device`, `gemm_precision` as in `map_cells_to_space`.
+    still resident in HBM instead (required when `adata_map.X` is the sparse top-k matrix of `top_k=`: ValueError otherwise); `device`, `gemm_precision` as in `map_cells_to_space`.
     Unlike the reference (`sc.pp.filter_genes`, `var_names_make_unique` mutate the caller's AnnData in place, :351-357),
     only `adata_sc.var.index` is rewritten in place; the gene filter and `n_cells` land on a view."""
     adata_sc.var.index = [g.lower() for g in adata_sc.var.index]                     # :351
@@ -85,6 +85,10 @@ def project_genes(adata_map, adata_sc, cluster_label=None, scale=True, *, mapper
     X_sc = adata_sc.X                                                                # :364-365: sparse stays sparse, the gene blocks
     S_all = X_sc if hasattr(X_sc, "tocsr") else np.ascontiguousarray(mu._dense(X_sc), dtype=np.float32)   # are expanded on the device
     own = mapper is None
+    if own and hasattr(adata_map.X, "tocsr"):
+        raise ValueError("adata_map.X is sparse (map_cells_to_space(..., top_k=k) keeps each cell's k most probable spots only): "
+                         "project with the trained mapping instead -- map with keep_mapper=True and pass "
+                         "mapper=adata_map._tangram_amd_mapper")
     if own:
         engine, rows = _projection_engine(adata_map, torch.device(device), gemm_precision)
     else:
