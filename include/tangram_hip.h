@@ -252,6 +252,33 @@ int tg_mapper_project_genes(tg_mapper* m, const float* S_dev, int64_t ld_s, int3
 int tg_csr_columns_to_dense(const int64_t* indptr_dev, const int32_t* indices_dev, const float* data_dev, int64_t n_rows,
                             int32_t col0, int32_t n_cols, float* out_dev, int64_t ld_out, void* hip_stream);
 
+/* ---- genes projected from a SPARSE mapping -----------------------------------------------------------------------------------
+ * `adata_map.X.T @ adata_sc.X` (utils.py:366-368) for an adata_map.X that is a cells x spots CSR matrix with a few entries per row
+ * (the top-k result above, reloaded from disk, thresholded by the user, ...): no handle, no logits, no cells x spots plane.  The
+ * three calls take no handle, enqueue on `hip_stream` and allocate nothing; TG_ERR_INVALID (never a fault) for a NULL pointer, a
+ * negative size, or n_cells / nnz above 2^31 - 1, n_spots above 2^31 - 2 (the 32-bit indices and grids of the kernels), or more
+ * entries than n_cells x n_spots.  The device code TRUSTS the arrays: the caller guarantees a canonical CSR (indptr monotone from 0
+ * to nnz, indices sorted inside a row, without duplicates, in [0, n_spots)).
+ *
+ * Bytes of the workspace of a mapping of this shape (the spot-major image + what building it needs).                            */
+int tg_sparse_map_query_bytes(int64_t n_cells, int64_t n_spots, int64_t nnz, size_t* bytes_out);
+
+/* Builds the spot-major image of the mapping into workspace_dev (8-byte aligned, tg_sparse_map_query_bytes bytes): per spot its
+ * (cell, value) entries, ORDERED BY ASCENDING CELL INDEX -- a pure function of the matrix, the same bits on every call.  indptr
+ * int64 [n_cells + 1], indices int32 [nnz], data float [nnz], on the device; indices / data may be NULL when nnz == 0.  Integer
+ * counters are bumped atomically, the order is fixed afterwards; no float atomics.  Build once, project any number of times.   */
+int tg_sparse_map_build(const int64_t* indptr_dev, const int32_t* indices_dev, const float* data_dev, int64_t n_cells,
+                        int64_t n_spots, int64_t nnz, void* workspace_dev, void* hip_stream);
+
+/* out_dev[n_spots][ld_out] (first n_genes columns; the others are not touched) = X^T S_dev, S_dev [n_cells][ld_s] holding n_genes
+ * columns; workspace_dev as tg_sparse_map_build left it, with the same three sizes.  Every element is ONE fp32 fmaf chain from 0
+ * over the entries of its spot in ascending cell order: the result is bit-reproducible and does not depend on the alignment of
+ * S_dev / out_dev / the pitches (16-byte accesses are used where those allow) nor on how a gene range is split over calls.  A spot
+ * without entries, and every spot when nnz == 0, gets zeros: out_dev may be uninitialised.  Also TG_ERR_INVALID: n_genes <= 0,
+ * ld_s < n_genes, ld_out < n_genes.                                                                                             */
+int tg_sparse_map_project(const void* workspace_dev, int64_t n_cells, int64_t n_spots, int64_t nnz, const float* S_dev,
+                          int64_t ld_s, int32_t n_genes, float* out_dev, int64_t ld_out, void* hip_stream);
+
 /* ---- batched independent mappings ------------------------------------------------------------------------------
  * The reference trains independent mappings one after the other: one per held-out gene in `cross_val` (utils.py:576-600; 249 in
  * the tutorial), three seeds per trial in the tuner (mapping_parameter_tuning.py:109-131).  A tg_batch advances B Mapper handles

@@ -88,6 +88,12 @@ def _declare(lib):
     lib.tg_mapper_project_genes.argtypes = [vp, vp, ct.c_int64, i32, vp, ct.c_int64, i32]
     lib.tg_csr_columns_to_dense.argtypes = [vp, vp, vp, ct.c_int64, i32, i32, vp, ct.c_int64, vp]
     lib.tg_csr_columns_to_dense.restype = i32
+    lib.tg_sparse_map_query_bytes.argtypes = [ct.c_int64, ct.c_int64, ct.c_int64, ct.POINTER(ct.c_size_t)]
+    lib.tg_sparse_map_build.argtypes = [vp, vp, vp, ct.c_int64, ct.c_int64, ct.c_int64, vp, vp]
+    lib.tg_sparse_map_project.argtypes = [vp, ct.c_int64, ct.c_int64, ct.c_int64, vp, ct.c_int64, ct.c_int32, vp, ct.c_int64, vp]
+    lib.tg_debug_sparse_map_layout.argtypes = [ct.c_int64, ct.c_int64, ct.POINTER(ct.c_int64)]
+    for name in ("tg_sparse_map_query_bytes", "tg_sparse_map_build", "tg_sparse_map_project", "tg_debug_sparse_map_layout"):
+        getattr(lib, name).restype = i32
     lib.tg_batch_query_bytes.argtypes = [i32]
     lib.tg_batch_query_bytes.restype = ct.c_size_t
     lib.tg_batch_create.argtypes = [ct.POINTER(vp), i32, vp, ct.POINTER(vp)]
@@ -124,7 +130,8 @@ EXPORTS = ["tg_abi_version", "tg_last_error", "tg_query_sizes", "tg_mapper_creat
            "tg_mapper_step", "tg_comm_create_callbacks", "tg_comm_rccl_unique_id", "tg_comm_create_rccl", "tg_comm_peer_create", "tg_comm_peer_create_stepped", "tg_comm_peer_connect", "tg_comm_peer_status", "tg_comm_peer_set_timeout_ms",
            "tg_comm_all_reduce_sum", "tg_comm_all_gather", "tg_comm_destroy",
            "tg_mapper_attach_comm", "tg_mapper_result", "tg_mapper_result_topk", "tg_topk_merge",
-           "tg_mapper_project", "tg_mapper_project_genes", "tg_csr_columns_to_dense", "tg_csr_gather_columns", "tg_row_sums",
+           "tg_mapper_project", "tg_mapper_project_genes", "tg_csr_columns_to_dense", "tg_sparse_map_query_bytes", "tg_sparse_map_build",
+           "tg_sparse_map_project", "tg_csr_gather_columns", "tg_row_sums",
            "tg_cluster_aggregate", "tg_batch_query_bytes", "tg_batch_create", "tg_batch_step", "tg_batch_destroy", "tg_mapper_state", "tg_mapper_set_step",
            "tg_mapper_filter_state", "tg_mapper_profile",
            "tg_mapper_profile_read", "tg_mapper_validate", "tg_init_logits_normal", "tg_mapper_effective_precision"]

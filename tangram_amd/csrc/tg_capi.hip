@@ -2106,6 +2106,79 @@ extern "C" int tg_csr_columns_to_dense(const int64_t* indptr_dev, const int32_t*
     return TG_OK;
 }
 
+// ---- genes projected from a sparse mapping (tg_sparse.h): no handle, the caller's workspace, the caller's stream
+static int tg_sparse_map_shape(const char* who, int64_t n_cells, int64_t n_spots, int64_t nnz) {
+    if (n_cells < 0 || n_spots < 0 || nnz < 0)
+        return tg_fail(TG_ERR_INVALID, "%s: negative size: cells %lld, spots %lld, entries %lld", who, (long long)n_cells, (long long)n_spots, (long long)nnz);
+    // cell and spot indices are int32, the per-entry grids have (nnz + 255) / 256 workgroups, tg_sp_order one workgroup per spot
+    if (n_cells > 0x7fffffffLL || n_spots > 0x7ffffffeLL || nnz > 0x7fffffffLL)
+        return tg_fail(TG_ERR_INVALID, "%s: cells %lld, spots %lld or entries %lld exceed the 32-bit indices and grids of the kernels (2^31 - 1)", who,
+                       (long long)n_cells, (long long)n_spots, (long long)nnz);
+    if ((unsigned __int128)nnz > (unsigned __int128)n_cells * (unsigned __int128)n_spots)
+        return tg_fail(TG_ERR_INVALID, "%s: %lld entries do not fit a canonical %lld x %lld matrix", who, (long long)nnz, (long long)n_cells, (long long)n_spots);
+    return TG_OK;
+}
+
+extern "C" int tg_sparse_map_query_bytes(int64_t n_cells, int64_t n_spots, int64_t nnz, size_t* bytes_out) {
+    if (!bytes_out) return tg_fail(TG_ERR_INVALID, "sparse map: bytes_out is NULL");
+    const int rc = tg_sparse_map_shape("sparse map", n_cells, n_spots, nnz);
+    if (rc) return rc;
+    *bytes_out = tg_sparse_map_layout(n_spots, nnz).bytes;
+    return TG_OK;
+}
+
+extern "C" int tg_sparse_map_build(const int64_t* indptr_dev, const int32_t* indices_dev, const float* data_dev, int64_t n_cells,
+                                   int64_t n_spots, int64_t nnz, void* workspace_dev, void* hip_stream) {
+    const int rc = tg_sparse_map_shape("sparse map build", n_cells, n_spots, nnz);
+    if (rc) return rc;
+    if (!indptr_dev || !workspace_dev || (nnz > 0 && (!indices_dev || !data_dev))) return tg_fail(TG_ERR_INVALID, "sparse map build: null argument");
+    const TgSparseMapLayout L = tg_sparse_map_layout(n_spots, nnz);
+    tg_stream_t s = (tg_stream_t)hip_stream;
+    unsigned char* ws = (unsigned char*)workspace_dev;
+    long long* spot_ptr = (long long*)(ws + L.o_ptr);
+    int* cnt = (int*)(ws + L.o_cnt);
+    int* tcell = (int*)(ws + L.o_tcell);
+    float* tval = (float*)(ws + L.o_tval);
+    const long long entry_grid = (nnz + 255) / 256;
+    if (n_spots > 0) TG_CK(tg_memset(cnt, 0, 4 * (size_t)n_spots, s));
+    if (nnz > 0) TG_LAUNCH(tg_sp_count, entry_grid, 1, 256, 0, s, (const int*)indices_dev, (long long)nnz, cnt);
+    TG_LAUNCH(tg_sp_scan, 1, 1, 1024, 1024 * 8, s, cnt, (long long)n_spots, spot_ptr);
+    if (nnz > 0) {
+        TG_LAUNCH(tg_sp_scatter, entry_grid, 1, 256, 0, s, (const long long*)indptr_dev, (const int*)indices_dev, data_dev, (int)n_cells,
+                  (long long)nnz, (const long long*)spot_ptr, cnt, tcell, tval);
+        TG_LAUNCH(tg_sp_order, n_spots, 1, 256, TG_SP_TILE * 4, s, (const long long*)spot_ptr, (const int*)tcell, (const float*)tval,
+                  (int*)(ws + L.o_cell), (float*)(ws + L.o_val));
+    }
+    TG_LAUNCH_CK();
+    return TG_OK;
+}
+
+extern "C" int tg_sparse_map_project(const void* workspace_dev, int64_t n_cells, int64_t n_spots, int64_t nnz, const float* S_dev,
+                                     int64_t ld_s, int32_t n_genes, float* out_dev, int64_t ld_out, void* hip_stream) {
+    const int rc = tg_sparse_map_shape("sparse map project", n_cells, n_spots, nnz);
+    if (rc) return rc;
+    if (!workspace_dev || !S_dev || !out_dev) return tg_fail(TG_ERR_INVALID, "sparse map project: null argument");
+    if (n_genes <= 0 || ld_s < n_genes || ld_out < n_genes)
+        return tg_fail(TG_ERR_INVALID, "sparse map project: n_genes %d must be positive and no larger than the pitches of S (%lld) and out (%lld)", n_genes,
+                       (long long)ld_s, (long long)ld_out);
+    const TgSparseMapLayout L = tg_sparse_map_layout(n_spots, nnz);
+    const unsigned char* ws = (const unsigned char*)workspace_dev;
+    TgSparseProjArgs a;
+    a.spot_ptr = (const long long*)(ws + L.o_ptr); a.cell = (const int*)(ws + L.o_cell); a.val = (const float*)(ws + L.o_val);
+    a.S = S_dev; a.ld_s = ld_s; a.n_genes = n_genes; a.out = out_dev; a.ld_out = ld_out;
+    // 16-byte accesses where every row segment a thread touches is 16-byte aligned: bases and pitches (tile offsets are multiples of 4 KB)
+    const bool vec = (((uintptr_t)S_dev | (uintptr_t)out_dev) & 15) == 0 && ld_s % 4 == 0 && ld_out % 4 == 0;
+    const long long ntiles = ((long long)n_genes + TG_SP_GENES - 1) / TG_SP_GENES;              // <= 2^21
+    const long long per_launch = (1LL << 30) / ntiles;                                           // spots per launch: grid <= 2^30
+    for (long long v0 = 0; v0 < n_spots; v0 += per_launch) {
+        a.v0 = (int)v0; a.nv = (int)(n_spots - v0 < per_launch ? n_spots - v0 : per_launch);
+        if (vec) TG_LAUNCH((tg_sp_project<true>), ntiles * a.nv, 1, 256, 0, (tg_stream_t)hip_stream, a);
+        else TG_LAUNCH((tg_sp_project<false>), ntiles * a.nv, 1, 256, 0, (tg_stream_t)hip_stream, a);
+    }
+    TG_LAUNCH_CK();
+    return TG_OK;
+}
+
 extern "C" int tg_csr_gather_columns(const int64_t* indptr_dev, const int32_t* indices_dev, const float* data_dev, int64_t n_rows,
                                      const int32_t* colmap_dev, int32_t n_out_cols, float* out_dev, int64_t ld_out, void* hip_stream) {
     if (!indptr_dev || !indices_dev || !data_dev || !colmap_dev || !out_dev) return tg_fail(TG_ERR_INVALID, "null argument");
@@ -2319,6 +2392,14 @@ extern "C" int tg_debug_fwd_cover(const tg_config* cfg, long long* out) {
 // the compile-time limits of tg_topk.h: out[0] = largest k, out[1] = spots per chunk of tg_row_topk
 extern "C" int tg_debug_topk_limits(int32_t out[2]) {
     out[0] = TG_TOPK_MAX; out[1] = TG_TOPK_CHUNK;
+    return TG_OK;
+}
+// where the spot-major image lies in a tg_sparse_map_build workspace: out[0..2] = byte offsets of spot_ptr (int64 [n_spots + 1]),
+// cell (int32 [nnz]) and val (float [nnz]); out[3] = genes per workgroup of tg_sp_project, out[4] = entries loaded ahead
+extern "C" int tg_debug_sparse_map_layout(int64_t n_spots, int64_t nnz, int64_t out[5]) {
+    if (n_spots < 0 || nnz < 0) return tg_fail(TG_ERR_INVALID, "negative size");
+    const TgSparseMapLayout L = tg_sparse_map_layout(n_spots, nnz);
+    out[0] = (int64_t)L.o_ptr; out[1] = (int64_t)L.o_cell; out[2] = (int64_t)L.o_val; out[3] = TG_SP_GENES; out[4] = TG_SP_AHEAD;
     return TG_OK;
 }
 // TEST HOOK: Adam's square root and divisions as the update kernels evaluate them (tg_device.h: tg_sqrt_cr, tg_div_fr, tg_div_by):

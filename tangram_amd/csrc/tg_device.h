@@ -85,6 +85,8 @@ TG_DEV void tg_dma_drain() {}
 TG_DEV void tg_flag_or(int* p, int v) { *p |= v; }
 // atomic add on a counter in LDS, returns the old value (one fiber runs at a time: a plain add)
 TG_DEV int tg_lds_atomic_add(int* p, int v) { const int old = *p; *p = old + v; return old; }
+// ... and on an INTEGER counter in global memory (workgroups run one after the other)
+TG_DEV int tg_global_atomic_add(int* p, int v) { const int old = *p; *p = old + v; return old; }
 // buffer-descriptor form of the copy (see the HIP build below): descriptor = {base pointer, byte count}
 struct TgRsrc { const unsigned char* base; unsigned bytes; };
 TG_DEV TgRsrc tg_make_rsrc(const unsigned char* base, size_t bytes) { return TgRsrc{base, (unsigned)bytes}; }
@@ -198,6 +200,9 @@ TG_DEV void tg_dma_drain() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 TG_DEV void tg_flag_or(int* p, int v) { atomicOr(p, v); }
 // atomic add on a counter in LDS, returns the old value (ds_add_rtn_u32)
 TG_DEV int tg_lds_atomic_add(int* p, int v) { return atomicAdd(p, v); }
+// atomic add on an INTEGER counter in global memory, device scope, returns the old value (global_atomic_add).  Integers only: a
+// count does not depend on the order of the adds -- float sums never go through atomics here.
+TG_DEV int tg_global_atomic_add(int* p, int v) { return atomicAdd(p, v); }
 // The copy through a BUFFER DESCRIPTOR: buffer_load_dwordx4 ... offen lds.  Source = descriptor base (SGPRs) + this lane's byte
 // offset (one VGPR, fixed for the whole tile) + soffset (an SGPR: the contraction step).  Against the global_load_lds form (64-bit
 // lane addresses rebuilt by two VALU instructions per copy and step) the loop carries no address arithmetic at all, and the copy

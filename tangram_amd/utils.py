@@ -60,7 +60,7 @@ def _projection_engine(adata_map, device, gemm_precision):
 
 
 def project_genes(adata_map, adata_sc, cluster_label=None, scale=True, *, mapper=None, device="cuda:0",
-                  gemm_precision="bf16x3"):
+                  gemm_precision="bf16x3", truncated=False):
     """Transfer gene expression from the single cell data onto space (reference utils.py:338-375).
 
     Like the reference, the projection is `adata_map.X.T @ adata_sc.X` of the mapping matrix the caller passes in (which
@@ -68,6 +68,13 @@ def project_genes(adata_map, adata_sc, cluster_label=None, scale=True, *, mapper
     Extra keywords: `mapper` -- pass the trained `Mapper`/`MapperConstrained` EXPLICITLY (e.g. the
     `adata_map._tangram_amd_mapper` of `map_cells_to_space(..., keep_mapper=True)`) to project with the mapping that is
     still resident in HBM instead (required when `adata_map.X` is the sparse top-k matrix of `top_k=`: ValueError otherwise); `device`, `gemm_precision` as in `map_cells_to_space`.
+    `truncated=True` -- project a SPARSE `adata_map.X` as it is: the result is `adata_map.X.T @ adata_sc.X` of exactly the matrix
+    passed in (the reference's definition, utils.py:366-368), computed on `device` by the sparse kernels (tangram_amd.sparse_project)
+    without a mapper, logits or a cells x spots plane -- so it works on a top-k result that was saved and reloaded, mapped in another
+    process, or whose mapper was released, and on a dense mapping thresholded into a sparse matrix.  The flag is explicit because
+    this is NOT the dense mapping's projection: a top-k matrix keeps only part of each cell's probability mass
+    (`adata_map.obs["top_k_mass"]`), nothing is renormalised, and every projected value is at most the dense one for non-negative
+    expression.  ValueError with a dense `adata_map.X` or together with `mapper=`.
     Unlike the reference (`sc.pp.filter_genes`, `var_names_make_unique` mutate the caller's AnnData in place, :351-357),
     only `adata_sc.var.index` is rewritten in place; the gene filter and `n_cells` land on a view."""
     adata_sc.var.index = [g.lower() for g in adata_sc.var.index]                     # :351
@@ -85,10 +92,21 @@ def project_genes(adata_map, adata_sc, cluster_label=None, scale=True, *, mapper
     X_sc = adata_sc.X                                                                # :364-365: sparse stays sparse, the gene blocks
     S_all = X_sc if hasattr(X_sc, "tocsr") else np.ascontiguousarray(mu._dense(X_sc), dtype=np.float32)   # are expanded on the device
     own = mapper is None
+    if truncated:
+        if not own:
+            raise ValueError("truncated=True projects the sparse adata_map.X itself: it cannot be combined with mapper=")
+        if not hasattr(adata_map.X, "tocsr"):
+            raise ValueError("truncated=True needs a sparse adata_map.X (the top_k= result); a dense mapping is projected without it")
+        from .sparse_project import SparseMap
+        X_space = SparseMap(adata_map.X, device, n_cells=S_all.shape[0]).project(S_all).cpu().numpy()      # :366, no renormalisation
+        adata_ge = _result(X_space, adata_map.var, adata_sc.var, adata_sc.uns)
+        training_genes = adata_map.uns["train_genes_df"].index.values
+        adata_ge.var["is_training"] = adata_ge.var.index.isin(training_genes)
+        return adata_ge
     if own and hasattr(adata_map.X, "tocsr"):
         raise ValueError("adata_map.X is sparse (map_cells_to_space(..., top_k=k) keeps each cell's k most probable spots only): "
                          "project with the trained mapping instead -- map with keep_mapper=True and pass "
-                         "mapper=adata_map._tangram_amd_mapper")
+                         "mapper=adata_map._tangram_amd_mapper -- or project the truncated matrix itself with truncated=True")
     if own:
         engine, rows = _projection_engine(adata_map, torch.device(device), gemm_precision)
     else:
