@@ -8,16 +8,21 @@
 #include <stdio.h>
 #include <string.h>
 
-#include <map>
 #include <new>
 #include <string>
 #include <type_traits>
 #include <vector>
 
+// TG_LAUNCH(kernel, shape, stream, args...): one launch of `kernel` with the TgShape `shape` (tg_device.h; tg_<kernel>_shape next to the
+// kernel, or tg_shape(gx, gy, block, lds) at the only launch site of a kernel); TG_LAUNCH_Z: the `nz` mappings of a batch in blockIdx.z.
+#define TG_LAUNCH(kern, shape, stream, ...) TG_LAUNCH_Z(kern, shape, 1, stream, __VA_ARGS__)
 #ifdef TG_SIM
 typedef void* tg_stream_t;
-#define TG_LAUNCH(kern, gx, gy, block, lds, stream, ...) \
-    hipsim::launch(hipsim::uint3s{(unsigned)(gx), (unsigned)(gy), 1u}, hipsim::uint3s{(unsigned)(block), 1u, 1u}, [&] { kern(__VA_ARGS__); })
+#define TG_LAUNCH_Z(kern, shape, nz, stream, ...)                                                                                 \
+    do {                                                                                                                          \
+        const TgShape _s = (shape);                                                                                               \
+        hipsim::launch(hipsim::uint3s{_s.gx, _s.gy, (unsigned)(nz)}, hipsim::uint3s{_s.block, 1u, 1u}, [&] { kern(__VA_ARGS__); }); \
+    } while (0)
 static int tg_memcpy2d(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height, tg_stream_t) {
     for (size_t r = 0; r < height; ++r) memcpy((char*)dst + r * dpitch, (const char*)src + r * spitch, width);
     return 0;
@@ -25,8 +30,6 @@ static int tg_memcpy2d(void* dst, size_t dpitch, const void* src, size_t spitch,
 static int tg_memset(void* dst, int v, size_t n, tg_stream_t) { memset(dst, v, n); return 0; }
 static int tg_memcpy_h2d(void* dst, const void* src, size_t n, tg_stream_t) { memcpy(dst, src, n); return 0; }
 static int tg_memcpy(void* dst, const void* src, size_t n, tg_stream_t) { memcpy(dst, src, n); return 0; }
-#define TG_LAUNCH3(kern, gx, gy, gz, block, lds, stream, ...) \
-    hipsim::launch(hipsim::uint3s{(unsigned)(gx), (unsigned)(gy), (unsigned)(gz)}, hipsim::uint3s{(unsigned)(block), 1u, 1u}, [&] { kern(__VA_ARGS__); })
 static int tg_launch_error(const char** name) { *name = nullptr; return 0; }
 static bool tg_launch_failed() { return false; }
 static const char* tg_hip_errstr(int) { return "emulator"; }
@@ -47,17 +50,10 @@ typedef hipStream_t tg_stream_t;
 // reported by tg_launch_status() -- a failed launch in the middle of a step is no longer an anonymous error at its end.
 static thread_local int g_launch_rc = 0;
 static thread_local const char* g_launch_name = nullptr;
-#define TG_LAUNCH(kern, gx, gy, block, lds, stream, ...)                                                                          \
+#define TG_LAUNCH_Z(kern, shape, nz, stream, ...)                                                                                 \
     do {                                                                                                                          \
-        hipLaunchKernelGGL(kern, dim3((unsigned)(gx), (unsigned)(gy), 1), dim3((unsigned)(block), 1, 1), (size_t)(lds), stream,   \
-                           __VA_ARGS__);                                                                                          \
-        const int _le = (int)hipGetLastError();                                                                                   \
-        if (_le != 0 && g_launch_rc == 0) { g_launch_rc = _le; g_launch_name = #kern; }                                           \
-    } while (0)
-#define TG_LAUNCH3(kern, gx, gy, gz, block, lds, stream, ...)                                                                      \
-    do {                                                                                                                          \
-        hipLaunchKernelGGL(kern, dim3((unsigned)(gx), (unsigned)(gy), (unsigned)(gz)), dim3((unsigned)(block), 1, 1), (size_t)(lds), \
-                           stream, __VA_ARGS__);                                                                                  \
+        const TgShape _s = (shape);                                                                                               \
+        hipLaunchKernelGGL(kern, dim3(_s.gx, _s.gy, (unsigned)(nz)), dim3(_s.block, 1, 1), _s.lds, stream, __VA_ARGS__);          \
         const int _le = (int)hipGetLastError();                                                                                   \
         if (_le != 0 && g_launch_rc == 0) { g_launch_rc = _le; g_launch_name = #kern; }                                           \
     } while (0)
@@ -140,6 +136,9 @@ struct TgLayout {
     // once, G) and evaluates the spatial terms redundantly on the whole graph; shards are then blocks of Vmaxl = ceil(Vtot / ranks)
     // spots (only the last one shorter), so that the gathered blocks ARE the global matrix.  Vsr = rows allocated (>= Vs).
     int Vs, Vsr, Vmaxl, sp_shard, nrb_s;
+    // Blocks of TG_RB spots, two counts each: nrb / nrb_s count the ALLOCATED rows Vr / Vsr and size buffers; grb / grb_s count the
+    // spots V / Vs themselves and are the grid x (and the partial rows summed) of the kernels that walk them.
+    int grb, grb_s;
     size_t o_GhatFull, o_Gfull;
     int smallc;                                       // C <= 32 (clusters mode): the iteration runs on tg_sc_forward / tg_sc_backward
     size_t o_Sa, o_Sx, o_spotpart;
@@ -304,6 +303,7 @@ static int tg_make_layout(const tg_config* cfg_in, TgLayout* L) {
     L->Vs = L->sp_shard ? L->Vtot : L->V;
     L->Vsr = L->sp_shard ? (int)rup((size_t)cfg->n_ranks * L->Vmaxl, TG_RB) : L->Vr;
     L->nrb_s = (L->Vsr + TG_RB - 1) / TG_RB;
+    L->grb = tg_row_blocks(L->V); L->grb_s = tg_row_blocks(L->Vs);
     L->full = (cfg->mode == TG_MODE_CONSTRAINED) || cfg->lambda_r != 0.f || cfg->lambda_l1 != 0.f || cfg->lambda_l2 != 0.f;
     const int nsteps = L->Cp / L->BKE;
     const int slots = 256 * (L->T == 256 ? 1 : 2);
@@ -537,22 +537,41 @@ TG_SELECT void tg_with_update_flags(bool full, bool x16, bool stream, F&& f) {
     tg_with_update_flags(full, x16, [&](auto fl, auto xh) { if (stream) f(fl, xh, tg_bool<true>{}); else f(fl, xh, tg_bool<false>{}); });
 }
 
+// backward GEMM (tg_bwd_kernel): <FULL, ROWDOT, STREAM>.  The ONLY list of its variants: tg_launch_bwd launches through it and tg_lds_attr
+// raises the LDS limit of every outcome.  `x_only` (no row dots: tg_adam_rowpass takes them) has its cached-access variant for the
+// single-GPU epilogue only: the row-dot variants serve spot shards and very long rows, i.e. big problems, and every GEMM instantiation
+// costs seconds of compile time.
+template <class F>
+TG_SELECT void tg_with_bwd_variant(bool x_only, bool stream_once, bool full, F&& f) {
+    if (x_only) { if (stream_once) f(tg_bool<false>{}, tg_bool<false>{}, tg_bool<true>{}); else f(tg_bool<false>{}, tg_bool<false>{}, tg_bool<false>{}); }
+    else if (full) f(tg_bool<true>{}, tg_bool<true>{}, tg_bool<true>{});
+    else f(tg_bool<false>{}, tg_bool<true>{}, tg_bool<true>{});
+}
+
+#ifndef TG_SIM
+static int tg_raise_lds(const void* kernel, int bytes) {
+    TG_CK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    return TG_OK;
+}
+#endif
 template <class PR, class GE>
 static int tg_lds_attr() {
+    int rc = TG_OK;
 #ifndef TG_SIM
-    const int bytes = GE::LDS_BYTES;
-    TG_CK(hipFuncSetAttribute((const void*)tg_fwd_kernel<PR, GE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    TG_CK(hipFuncSetAttribute((const void*)tg_fwd_kernel_b<PR, GE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    auto raise = [&](const void* kernel, int bytes) { if (rc == TG_OK) rc = tg_raise_lds(kernel, bytes); };
+    raise((const void*)tg_fwd_kernel<PR, GE>, GE::LDS_BYTES);
+    raise((const void*)tg_fwd_kernel_b<PR, GE>, GE::LDS_BYTES);
     if constexpr (GE::TM == 256 && PR::NP == 2) {
-        TG_CK(hipFuncSetAttribute((const void*)tg_fwd_kernel<PR, TgGeoWide>, hipFuncAttributeMaxDynamicSharedMemorySize, TgGeoWide::LDS_BYTES));
-        TG_CK(hipFuncSetAttribute((const void*)tg_fwd_kernel_b<PR, TgGeoWide>, hipFuncAttributeMaxDynamicSharedMemorySize, TgGeoWide::LDS_BYTES));
+        raise((const void*)tg_fwd_kernel<PR, TgGeoWide>, TgGeoWide::LDS_BYTES);
+        raise((const void*)tg_fwd_kernel_b<PR, TgGeoWide>, TgGeoWide::LDS_BYTES);
     }
-    TG_CK(hipFuncSetAttribute((const void*)tg_bwd_kernel_b<PR, GE>, hipFuncAttributeMaxDynamicSharedMemorySize, GE::BWD_LDS_BYTES));
-#define TG_BWD_ATTR(F, R, S) TG_CK(hipFuncSetAttribute((const void*)tg_bwd_kernel<PR, GE, F, R, S>, hipFuncAttributeMaxDynamicSharedMemorySize, GE::BWD_LDS_BYTES))
-    TG_BWD_ATTR(false, true, true); TG_BWD_ATTR(true, true, true); TG_BWD_ATTR(false, false, true); TG_BWD_ATTR(false, false, false);
-#undef TG_BWD_ATTR
+    raise((const void*)tg_bwd_kernel_b<PR, GE>, GE::BWD_LDS_BYTES);
+    for (int i = 0; i < 8; ++i)                          // every (x_only, stream_once, full): each variant of the selector
+        tg_with_bwd_variant(i & 1, i & 2, i & 4, [&](auto fl, auto rd, auto so) {
+            raise((const void*)tg_bwd_kernel<PR, GE, decltype(fl)::value, decltype(rd)::value, decltype(so)::value>, GE::BWD_LDS_BYTES);
+        });
 #endif
-    return TG_OK;
+    return rc;
 }
 template <class PR>
 static int tg_lds_attr_layout(const TgLayout& L) {        // ... of the layout's own tile geometry
@@ -593,7 +612,7 @@ static int tg_s_is_exact(tg_mapper* m, const tg_inputs* in, int* exact) {
     int* flag = (int*)(m->fp(L.o_fsum) + 48);              // (64 floats of scratch, zeroed with the workspace; [0] is the filter sum)
     const size_t n = (size_t)L.C * (L.K + 1 + L.T_ct);
     const int grid = (int)(n / 1024 + 1 < 4096 ? n / 1024 + 1 : 4096);
-    TG_LAUNCH(tg_s_exact_check, grid, 1, 256, 0, m->stream, tg_prep_s_args(m, in), flag);
+    TG_LAUNCH(tg_s_exact_check, tg_shape(grid, 1, 256, 0), m->stream, tg_prep_s_args(m, in), flag);
     TG_LAUNCH_CK();
     int h = 1;
 #ifdef TG_SIM
@@ -612,12 +631,12 @@ static int tg_setup_operands(tg_mapper* m, const tg_inputs* in) {
     const TgLayout& L = m->L;
     const TgPrepSArgs a = tg_prep_s_args(m, in);
     const size_t n1 = (size_t)L.Cr * (L.Kp / PR::CH), n2 = (size_t)L.Kp * (L.Cp / PR::CH);
-    TG_LAUNCH((tg_prep_sk<PR>), (n1 + 255) / 256, 1, 256, 0, m->stream, a);
-    TG_LAUNCH((tg_prep_st<PR>), (n2 + 255) / 256, 1, 256, 0, m->stream, a);
+    TG_LAUNCH((tg_prep_sk<PR>), tg_prep_s_shape(n1), m->stream, a);
+    TG_LAUNCH((tg_prep_st<PR>), tg_prep_s_shape(n2), m->stream, a);
     TG_LAUNCH_CK();
     if (L.smallc) {
         const int cm = tg_sc_cm(L.C);
-        TG_LAUNCH(tg_prep_ssmall, (16 * ((cm + 15) / 16) * L.Kp + 255) / 256, 1, 256, 0, m->stream, in->S_dev, (long long)L.K, a.aug, L.C, cm, L.K, L.Kp, m->fp(L.o_Sa),
+        TG_LAUNCH(tg_prep_ssmall, tg_shape((16 * ((cm + 15) / 16) * L.Kp + 255) / 256, 1, 256, 0), m->stream, in->S_dev, (long long)L.K, a.aug, L.C, cm, L.K, L.Kp, m->fp(L.o_Sa),
                   m->fp(L.o_Sx));
         TG_LAUNCH_CK();
     }
@@ -628,7 +647,7 @@ static int tg_setup_operands(tg_mapper* m, const tg_inputs* in) {
 static int tg_softmax_stats_from_scratch(tg_mapper* m) {
     const TgLayout& L = m->L;
     float* M = (float*)(m->st + L.s_M);
-    TG_LAUNCH(tg_row_stats, L.C, 1, 256, 64, m->stream, (const float*)M, L.C, L.V, L.Vp, m->fp(L.o_rowpair));
+    TG_LAUNCH(tg_row_stats, tg_shape(L.C, 1, 256, 64), m->stream, (const float*)M, L.C, L.V, L.Vp, m->fp(L.o_rowpair));
     TG_LAUNCH_CK();
     return TG_OK;
 }
@@ -650,7 +669,7 @@ static int tg_merge(tg_mapper* m, const float* parts, int nparts, bool finalize,
                     int rank = 0) {
     const TgLayout& L = m->L;
     const TgMergeArgs a = tg_merge_args(m, parts, nparts, finalize, want_pair, global_hist_row, rank);
-    TG_LAUNCH(tg_merge_stats, (L.C + 255) / 256, 1, 256, 0, m->stream, a);
+    TG_LAUNCH(tg_merge_stats, tg_merge_stats_shape(L.C), m->stream, a);
     tg_prof_mark(m, "tg_merge_stats");
     TG_LAUNCH_CK();
     return TG_OK;
@@ -697,10 +716,9 @@ static int tg_setup_spatial_derived(tg_mapper* m) {
         TgSpmmArgs a = {};
         a.W = tg_csr(m, 0); a.A = tg_sp_g(m); a.B = nullptr; a.ca = nullptr; a.cb = nullptr;
         a.Y = m->fp(L.o_WG); a.V = L.Vs; a.Kp = L.Kp; a.k_begin = 0; a.k_end = L.K;
-        TG_LAUNCH(tg_spmm, L.Vs, 1, 256, 0, m->stream, a);
-        const int nrb = (L.Vs + TG_RB - 1) / TG_RB;
-        TG_LAUNCH(tg_colstats, nrb, 1, 256, 0, m->stream, (const float*)m->fp(L.o_WG), (const float*)m->fp(L.o_WG), L.Vs, L.Kp, m->fp(L.o_nbpart));
-        TG_LAUNCH(tg_gene_reduce, (L.Kp + 63) / 64, 1, 1024, TG_GR_GROUPS * 64 * 2 * 4, m->stream, (const float*)m->fp(L.o_nbpart), nrb, L.Kp, m->fp(L.o_wgn2));
+        TG_LAUNCH(tg_spmm, tg_spmm_shape(L.Vs), m->stream, a);
+        TG_LAUNCH(tg_colstats, tg_spot_blocks_shape(L.Vs), m->stream, (const float*)m->fp(L.o_WG), (const float*)m->fp(L.o_WG), L.Vs, L.Kp, m->fp(L.o_nbpart));
+        TG_LAUNCH(tg_gene_reduce, tg_gene_reduce_shape(L.Kp, false), m->stream, (const float*)m->fp(L.o_nbpart), L.grb_s, L.Kp, m->fp(L.o_wgn2));
         TG_LAUNCH_CK();
     }
     return TG_OK;
@@ -713,19 +731,18 @@ static int tg_launch_spatial_stats(tg_mapper* m) {
         TgSpmmArgs a = {};
         a.W = tg_csr(m, 0); a.A = tg_sp_ghat(m); a.B = nullptr; a.ca = nullptr; a.cb = nullptr;
         a.Y = m->fp(L.o_Y); a.V = L.Vs; a.Kp = L.Kp; a.k_begin = 0; a.k_end = L.K;
-        TG_LAUNCH(tg_spmm, L.Vs, 1, 256, 0, m->stream, a);
-        const int nrb = (L.Vs + TG_RB - 1) / TG_RB;
-        TG_LAUNCH(tg_colstats, nrb, 1, 256, 0, m->stream, (const float*)m->fp(L.o_Y), (const float*)m->fp(L.o_WG), L.Vs, L.Kp, m->fp(L.o_nbpart));
-        TG_LAUNCH(tg_gene_reduce, (L.Kp + 63) / 64, 1, 1024, TG_GR_GROUPS * 64 * 2 * 4, m->stream, (const float*)m->fp(L.o_nbpart), nrb, L.Kp, m->fp(L.o_nbstat));
+        TG_LAUNCH(tg_spmm, tg_spmm_shape(L.Vs), m->stream, a);
+        TG_LAUNCH(tg_colstats, tg_spot_blocks_shape(L.Vs), m->stream, (const float*)m->fp(L.o_Y), (const float*)m->fp(L.o_WG), L.Vs, L.Kp, m->fp(L.o_nbpart));
+        TG_LAUNCH(tg_gene_reduce, tg_gene_reduce_shape(L.Kp, false), m->stream, (const float*)m->fp(L.o_nbpart), L.grb_s, L.Kp, m->fp(L.o_nbstat));
         tg_prof_mark(m, "tg_spatial_nb_stats");
     }
     if (L.has_ct) {
         TgCtArgs c;
         c.N = tg_csr(m, 2); c.Ghat = tg_sp_ghat(m); c.mask = m->fp(L.o_ctmask); c.ctpart = m->fp(L.o_ctpart);
         c.extra = m->fp(L.o_extra); c.V = L.Vs; c.Kp = L.Kp; c.K = L.K; c.T = L.T_ct; c.Tp = L.Tp; c.lambda_ct = m->cfg.lambda_ct_islands;
-        TG_LAUNCH(tg_ct_mask, L.Vs, 1, 64, 0, m->stream, c);
+        TG_LAUNCH(tg_ct_mask, tg_shape(L.Vs, 1, 64, 0), m->stream, c);
         c.N = tg_csr(m, 3);
-        TG_LAUNCH(tg_ct_grad, L.Vs, 1, 64, 0, m->stream, c);
+        TG_LAUNCH(tg_ct_grad, tg_shape(L.Vs, 1, 64, 0), m->stream, c);
         tg_prof_mark(m, "tg_spatial_ct");
     }
     return TG_OK;
@@ -748,30 +765,30 @@ static TgAcArgs tg_ac_args(tg_mapper* m, const float* X, bool setup, float* hist
 // Y = Ws X (+ local Geary sums into D), first and second stage statistics
 static void tg_ac_indicators(tg_mapper* m, TgAcArgs& a) {
     const TgLayout& L = m->L;
-    const int nrb = (L.Vs + TG_RB - 1) / TG_RB, kb = (L.Kp + 255) / 256;
+    const TgShape blocks = tg_spot_blocks_shape(L.Vs), reduce = tg_stat_reduce_shape(L.Kp);
     TgSpmmArgs sp = {};
     sp.W = tg_csr(m, 4); sp.A = a.X; sp.Y = m->fp(L.o_acY); sp.E = m->fp(L.o_acD); sp.V = L.Vs; sp.Kp = L.Kp; sp.k_begin = 0; sp.k_end = L.K;
-    TG_LAUNCH(tg_spmm, L.Vs, 1, 256, 0, m->stream, sp);
-    TG_LAUNCH(tg_ac_stats1, nrb, 1, 256, 0, m->stream, a);
-    TG_LAUNCH(tg_stat_reduce, kb, 1, 256, 0, m->stream, (const float*)a.part, nrb, (int)TGAC_NSTAT, L.Kp, a.stat);
-    TG_LAUNCH(tg_ac_stats2, nrb, 1, 256, 0, m->stream, a);
-    TG_LAUNCH(tg_stat_reduce, kb, 1, 256, 0, m->stream, (const float*)a.part, nrb, 3, L.Kp, a.stat2);
+    TG_LAUNCH(tg_spmm, tg_spmm_shape(L.Vs), m->stream, sp);
+    TG_LAUNCH(tg_ac_stats1, blocks, m->stream, a);
+    TG_LAUNCH(tg_stat_reduce, reduce, m->stream, (const float*)a.part, L.grb_s, (int)TGAC_NSTAT, L.Kp, a.stat);
+    TG_LAUNCH(tg_ac_stats2, blocks, m->stream, a);
+    TG_LAUNCH(tg_stat_reduce, reduce, m->stream, (const float*)a.part, L.grb_s, 3, L.Kp, a.stat2);
 }
 
 static int tg_setup_autocorr(tg_mapper* m) {
     const TgLayout& L = m->L;
-    const int nrb = (L.Vs + TG_RB - 1) / TG_RB;
-    TG_LAUNCH(tg_csr_rowsum, (L.Vs + 255) / 256, 1, 256, 0, m->stream, tg_csr(m, 4), L.Vs, m->fp(L.o_acr), 0);
-    TG_LAUNCH(tg_csr_rowsum, (L.Vs + 255) / 256, 1, 256, 0, m->stream, tg_csr(m, 4), L.Vs, m->fp(L.o_acrc), 0);
-    TG_LAUNCH(tg_csr_rowsum, (L.Vs + 255) / 256, 1, 256, 0, m->stream, tg_csr(m, 5), L.Vs, m->fp(L.o_acrc), 1);
+    const TgShape blocks = tg_spot_blocks_shape(L.Vs);
+    TG_LAUNCH(tg_csr_rowsum, tg_csr_rowsum_shape(L.Vs), m->stream, tg_csr(m, 4), L.Vs, m->fp(L.o_acr), 0);
+    TG_LAUNCH(tg_csr_rowsum, tg_csr_rowsum_shape(L.Vs), m->stream, tg_csr(m, 4), L.Vs, m->fp(L.o_acrc), 0);
+    TG_LAUNCH(tg_csr_rowsum, tg_csr_rowsum_shape(L.Vs), m->stream, tg_csr(m, 5), L.Vs, m->fp(L.o_acrc), 1);
     TgAcArgs a = tg_ac_args(m, tg_sp_g(m), true, nullptr);       // indicators of G: the references (:144)
     tg_ac_indicators(m, a);
-    TG_LAUNCH(tg_ac_refs, nrb, 1, 256, 0, m->stream, a);
+    TG_LAUNCH(tg_ac_refs, blocks, m->stream, a);
     // |Tg_k|^2 and |Tm_k|^2 (rows 0 and 2 of tnorm)
-    TG_LAUNCH(tg_colstats, nrb, 1, 256, 0, m->stream, (const float*)a.Tg, (const float*)a.Tg, L.Vs, L.Kp, a.part);
-    TG_LAUNCH(tg_gene_reduce, (L.Kp + 63) / 64, 1, 1024, TG_GR_GROUPS * 64 * 2 * 4, m->stream, (const float*)a.part, nrb, L.Kp, m->fp(L.o_actnorm));
-    TG_LAUNCH(tg_colstats, nrb, 1, 256, 0, m->stream, (const float*)a.Tm, (const float*)a.Tm, L.Vs, L.Kp, a.part);
-    TG_LAUNCH(tg_gene_reduce, (L.Kp + 63) / 64, 1, 1024, TG_GR_GROUPS * 64 * 2 * 4, m->stream, (const float*)a.part, nrb, L.Kp, m->fp(L.o_actnorm) + 2 * (size_t)L.Kp);
+    TG_LAUNCH(tg_colstats, blocks, m->stream, (const float*)a.Tg, (const float*)a.Tg, L.Vs, L.Kp, a.part);
+    TG_LAUNCH(tg_gene_reduce, tg_gene_reduce_shape(L.Kp, false), m->stream, (const float*)a.part, L.grb_s, L.Kp, m->fp(L.o_actnorm));
+    TG_LAUNCH(tg_colstats, blocks, m->stream, (const float*)a.Tm, (const float*)a.Tm, L.Vs, L.Kp, a.part);
+    TG_LAUNCH(tg_gene_reduce, tg_gene_reduce_shape(L.Kp, false), m->stream, (const float*)a.part, L.grb_s, L.Kp, m->fp(L.o_actnorm) + 2 * (size_t)L.Kp);
     TG_LAUNCH_CK();
     return TG_OK;
 }
@@ -779,22 +796,21 @@ static int tg_setup_autocorr(tg_mapper* m) {
 // per iteration, after tg_loss_finalize (which starts the history row)
 static int tg_launch_autocorr(tg_mapper* m, float* hist_row) {
     const TgLayout& L = m->L;
-    const int nrb = (L.Vs + TG_RB - 1) / TG_RB, kb = (L.Kp + 255) / 256;
     TgAcArgs a = tg_ac_args(m, tg_sp_ghat(m), false, hist_row);
     tg_ac_indicators(m, a);
     if (a.lam_geary > 0.f) {
         TgSpmmArgs sz = {};
         sz.W = tg_csr(m, 5); sz.A = a.X; sz.Y = m->fp(L.o_acZ); sz.V = L.Vs; sz.Kp = L.Kp; sz.k_begin = 0; sz.k_end = L.K;
-        TG_LAUNCH(tg_spmm, L.Vs, 1, 256, 0, m->stream, sz);
+        TG_LAUNCH(tg_spmm, tg_spmm_shape(L.Vs), m->stream, sz);
     }
     TgAcFinArgs f; f.a = a; f.tnorm = m->fp(L.o_actnorm);
-    TG_LAUNCH(tg_ac_finalize, 1, 1, 1024, 64, m->stream, f);
-    TG_LAUNCH(tg_ac_grad, nrb, 1, 256, 0, m->stream, a);
-    TG_LAUNCH(tg_stat_reduce, kb, 1, 256, 0, m->stream, (const float*)a.cmpart, nrb, 1, L.Kp, a.cm);
+    TG_LAUNCH(tg_ac_finalize, tg_shape(1, 1, 1024, 64), m->stream, f);
+    TG_LAUNCH(tg_ac_grad, tg_spot_blocks_shape(L.Vs), m->stream, a);
+    TG_LAUNCH(tg_stat_reduce, tg_stat_reduce_shape(L.Kp), m->stream, (const float*)a.cmpart, L.grb_s, 1, L.Kp, a.cm);
     TgSpmmArgs sg = {};       // extra[:, :K] (+)= Ws^T B1 + D - cm
     sg.W = tg_csr(m, 5); sg.A = a.B1; sg.Y = m->fp(L.o_extra); sg.V = L.Vs; sg.Kp = L.Kp; sg.k_begin = 0; sg.k_end = L.K;
     sg.accumulate = L.has_nb ? 1 : 0; sg.addD = a.D; sg.addc = a.cm;
-    TG_LAUNCH(tg_spmm, L.Vs, 1, 256, 0, m->stream, sg);
+    TG_LAUNCH(tg_spmm, tg_spmm_shape(L.Vs), m->stream, sg);
     tg_prof_mark(m, "tg_spatial_autocorr");
     return TG_OK;
 }
@@ -806,10 +822,18 @@ static int tg_launch_spatial_grad(tg_mapper* m) {
         TgSpmmArgs a = {};
         a.W = tg_csr(m, 1); a.A = m->fp(L.o_WG); a.B = m->fp(L.o_Y); a.ca = m->fp(L.o_nbcoef); a.cb = m->fp(L.o_nbcoef) + L.Kp;
         a.Y = m->fp(L.o_extra); a.V = L.Vs; a.Kp = L.Kp; a.k_begin = 0; a.k_end = L.K;
-        TG_LAUNCH(tg_spmm, L.Vs, 1, 256, 0, m->stream, a);
+        TG_LAUNCH(tg_spmm, tg_spmm_shape(L.Vs), m->stream, a);
         tg_prof_mark(m, "tg_spatial_nb_grad");
     }
     return TG_OK;
+}
+
+// Adam's bias-corrected step constants of the step after `step`, in double: the ONE place they are computed -- the solo steps
+// (tg_update_args, tg_filter_args) and the batch (TgStepVar) are bit-identical because they share it
+struct TgAdamStep { float step_size, bc2_sqrt; };
+static TgAdamStep tg_adam_step(const tg_config& cfg, int64_t step, float lr) {
+    const double t = (double)(step + 1);
+    return TgAdamStep{(float)((double)lr / (1.0 - pow((double)cfg.beta1, t))), (float)sqrt(1.0 - pow((double)cfg.beta2, t))};
 }
 
 static TgFilterArgs tg_filter_args(tg_mapper* m, bool update, float lr, float* hist_row) {
@@ -822,15 +846,14 @@ static TgFilterArgs tg_filter_args(tg_mapper* m, bool update, float lr, float* h
     a.C = L.C; a.do_update = update ? 1 : 0; a.has_density = m->cfg.has_density;
     a.lambda_d = m->cfg.lambda_d; a.lambda_count = m->cfg.lambda_count; a.lambda_f_reg = m->cfg.lambda_f_reg;
     a.target_count = m->cfg.target_count;
-    const double t = (double)(m->step + 1);
-    a.step_size = (float)((double)lr / (1.0 - pow((double)m->cfg.beta1, t)));
-    a.bc2_sqrt = (float)sqrt(1.0 - pow((double)m->cfg.beta2, t));
+    const TgAdamStep as = tg_adam_step(m->cfg, m->step, lr);
+    a.step_size = as.step_size; a.bc2_sqrt = as.bc2_sqrt;
     a.beta1 = m->cfg.beta1; a.beta2 = m->cfg.beta2; a.eps = m->cfg.eps;
     return a;
 }
 static int tg_launch_filter(tg_mapper* m, bool update, float lr, float* hist_row) {
     const TgFilterArgs a = tg_filter_args(m, update, lr, hist_row);
-    TG_LAUNCH(tg_filter_kernel, 1, 1, 1024, 64, m->stream, a);
+    TG_LAUNCH(tg_filter_kernel, tg_filter_shape(), m->stream, a);
     tg_prof_mark(m, "tg_filter_kernel");
     return TG_OK;
 }
@@ -884,21 +907,21 @@ extern "C" int tg_mapper_create(const tg_config* cfg, const tg_inputs* in, void*
     if (rc) return bail(rc);
     // padded G, |G_v|^2, |G_k|^2 partials (reuse genepart as scratch)
     // (genepart [nrb][2][Kp] doubles as scratch: first half |G|^2 partials, second half non-zero counts)
-    TG_LAUNCH(tg_prep_g, L.nrb, 1, 256, 4 * TG_RB * 4, m->stream, in->G_dev, L.V, L.K, L.Vr, L.Kp, m->fp(L.o_Gp),
+    TG_LAUNCH(tg_prep_g, tg_shape(L.nrb, 1, 256, 4 * TG_RB * 4), m->stream, in->G_dev, L.V, L.K, L.Vr, L.Kp, m->fp(L.o_Gp),
               m->fp(L.o_vnorm2), m->fp(L.o_genepart), m->fp(L.o_genepart) + (size_t)L.nrb * L.Kp);
-    TG_LAUNCH(tg_colsum_parts, (L.Kp + 63) / 64, 1, 1024, 16 * 64 * 4, m->stream, (const float*)m->fp(L.o_genepart), L.nrb, L.Kp,
+    const TgShape colsum = tg_shape((L.Kp + 63) / 64, 1, 1024, 16 * 64 * 4);
+    TG_LAUNCH(tg_colsum_parts, colsum, m->stream, (const float*)m->fp(L.o_genepart), L.nrb, L.Kp,
               m->fp(L.o_gnorm2), 1.f);
-    TG_LAUNCH(tg_colsum_parts, (L.Kp + 63) / 64, 1, 1024, 16 * 64 * 4, m->stream,
+    TG_LAUNCH(tg_colsum_parts, colsum, m->stream,
               (const float*)(m->fp(L.o_genepart) + (size_t)L.nrb * L.Kp), L.nrb, L.Kp, m->fp(L.o_gfrac), 1.f / (float)L.V);
-    if (cfg->has_density) TG_LAUNCH(tg_vec_sum, 1, 1, 1024, 64, m->stream, (const float*)m->fp(L.o_d), L.V, m->fp(L.o_gnorm2) + L.Kp);
+    if (cfg->has_density) TG_LAUNCH(tg_vec_sum, tg_shape(1, 1, 1024, 64), m->stream, (const float*)m->fp(L.o_d), L.V, m->fp(L.o_gnorm2) + L.Kp);
     if ((L.has_nb || L.has_ct || L.has_ac) && (rc = tg_setup_spatial(m, in))) return bail(rc);
     if (!L.sp_shard) {                      // (a spot shard derives these at tg_mapper_attach_comm, from the gathered G)
         if ((L.has_nb || L.has_ct || L.has_ac) && (rc = tg_setup_spatial_derived(m))) return bail(rc);
         if (L.has_ac && (rc = tg_setup_autocorr(m))) return bail(rc);
     }
     // padding of the softmax statistics: shift = +3e38, scale = 0  => exp(M - shift) * scale == 0
-    TG_LAUNCH(tg_fill, (L.Cp + 255) / 256, 1, 256, 0, m->stream, m->fp(L.o_rshift), (size_t)L.Cp, 3.0e38f);
-    TG_LAUNCH(tg_fill, (L.Cp + 255) / 256, 1, 256, 0, m->stream, m->fp(L.o_rscale), (size_t)L.Cp, 3.0e38f);
+    for (float* pad : {m->fp(L.o_rshift), m->fp(L.o_rscale)}) TG_LAUNCH(tg_fill, tg_shape((L.Cp + 255) / 256, 1, 256, 0), m->stream, pad, (size_t)L.Cp, 3.0e38f);
     if ((rc = tg_launch_status())) return bail(rc);
     if (cfg->mode == TG_MODE_CONSTRAINED) {
         if (tg_memcpy(m->st + L.s_F, in->F0_dev, (size_t)L.C * 4, m->stream)) return bail(tg_fail(TG_ERR_HIP, "copy of F0 failed"));
@@ -930,8 +953,12 @@ static void tg_band_range(const TgLayout& L, int b, int* ct0, int* ct1, int* c0,
     *c1 = (*ct1 * L.T < L.C) ? *ct1 * L.T : L.C;
 }
 
+// spot / gene tiles of the forward GEMM's geometry (tg_with_fwd_geo)
+static int tg_fwd_nvt(const TgLayout& L) { return L.fwd_wide ? L.Vr / 128 : L.nvt; }
+static int tg_fwd_nkt(const TgLayout& L) { return L.fwd_wide ? L.Kp / 512 : L.nkt; }
+
 template <class PR>
-static TgFwdArgs tg_fwd_args(tg_mapper* m, int band, const unsigned char* St_alt, bool unfiltered, int* grid_out) {
+static TgFwdArgs tg_fwd_args(tg_mapper* m, int band, const unsigned char* St_alt, bool unfiltered) {
     const TgLayout& L = m->L;
     TgFwdArgs a;
     a.M = (const float*)(m->st + L.s_M);
@@ -941,11 +968,9 @@ static TgFwdArgs tg_fwd_args(tg_mapper* m, int band, const unsigned char* St_alt
     a.St = St_alt ? St_alt : m->ws + L.o_St;
     a.Gpart = m->fp(L.o_Gpart);
     a.C = L.C; a.V = L.V; a.Vp = L.Vp; a.Vr = L.Vr; a.Kp = L.Kp; a.Cp = L.Cp;
-    const int nvt = L.fwd_wide ? L.Vr / 128 : L.nvt, nkt = L.fwd_wide ? L.Kp / 512 : L.nkt;
-    a.nkt = nkt; a.nvt = nvt; a.nsplit = L.nsplit; a.nsteps = L.Cp / PR::BKE;
+    a.nkt = tg_fwd_nkt(L); a.nvt = tg_fwd_nvt(L); a.nsplit = L.nsplit; a.nsteps = L.Cp / PR::BKE;
     a.units = L.fwd_units;
     a.band_index = 0; a.band_step_begin = 0; a.band_step_end = 0;
-    int grid = (L.fwd_units % nvt == 0) ? tg_fwd_grid(nvt, nkt, L.fwd_units / nvt) : tg_fwd_units_grid(L.fwd_units, nkt);
     if (band >= 0) {
         int ct0, ct1, c0, c1;
         tg_band_range(L, band, &ct0, &ct1, &c0, &c1);
@@ -953,9 +978,7 @@ static TgFwdArgs tg_fwd_args(tg_mapper* m, int band, const unsigned char* St_alt
         a.band_step_begin = c0 / PR::BKE;
         a.band_step_end = (band == L.bands - 1) ? a.nsteps : (ct1 * L.T) / PR::BKE;
         if (a.band_step_end > a.nsteps) a.band_step_end = a.nsteps;
-        grid = tg_fwd_grid(nvt, nkt, 1);
     }
-    *grid_out = grid;
     return a;
 }
 
@@ -964,11 +987,10 @@ static int tg_launch_forward(tg_mapper* m, tg_stream_t stream = nullptr, int ban
                              const unsigned char* St_alt = nullptr, bool unfiltered = false) {
     const TgLayout& L = m->L;
     if (band < 0) stream = m->stream;
-    int grid;
-    const TgFwdArgs a = tg_fwd_args<PR>(m, band, St_alt, unfiltered, &grid);
+    const TgFwdArgs a = tg_fwd_args<PR>(m, band, St_alt, unfiltered);
     tg_with_fwd_geo<PR>(L, [&](auto ge) {
         using GE = typename decltype(ge)::type;
-        TG_LAUNCH((tg_fwd_kernel<PR, GE>), grid, 1, GE::NT, GE::LDS_BYTES, stream, a);
+        TG_LAUNCH((tg_fwd_kernel<PR, GE>), tg_fwd_shape<GE>(a.nvt, a.nkt, a.units, band >= 0), stream, a);
     });
     if (band < 0) tg_prof_mark(m, "tg_fwd_kernel");
     return TG_OK;
@@ -984,25 +1006,20 @@ static TgGhatReduceArgs tg_ghat_args(tg_mapper* m, bool force_vox) {
     return a;
 }
 
-// many row blocks, e.g. 10 000 spots: tg_gene_reduce_tall(_x), 16 genes x 64 groups per workgroup (another order of the sums)
-static bool tg_gene_reduce_is_tall(int nrb) { return nrb > 512; }
 struct TgPeerLink;
 static int tg_launch_ghat_stats(tg_mapper* m, bool force_vox = false, const TgPeerLink* link = nullptr) {
     const TgLayout& L = m->L;
     const TgGhatReduceArgs a = tg_ghat_args(m, force_vox);
-    const int nrb = (L.V + TG_RB - 1) / TG_RB;
-    TG_LAUNCH(tg_ghat_reduce, nrb, (L.Kp + TG_GH_COLS - 1) / TG_GH_COLS, 256, 4 * 64 * 2 * 16, m->stream, a);
+    TG_LAUNCH(tg_ghat_reduce, tg_ghat_reduce_shape(L.V, L.Kp), m->stream, a);
     tg_prof_mark(m, "tg_ghat_reduce");
+    const bool tall = tg_gene_reduce_is_tall(L.grb);
+    const TgShape shape = tg_gene_reduce_shape(L.Kp, tall);
+    const float* part = m->fp(L.o_genepart);
     if (link) {                   // spot shard, peer transport: the exchange of the statistics happens inside this kernel
-        if (tg_gene_reduce_is_tall(nrb)) TG_LAUNCH(tg_gene_reduce_tall_x, (L.Kp + 15) / 16, 1, 1024, TG_GR_GROUPS * 64 * 2 * 4, m->stream, (const float*)m->fp(L.o_genepart), nrb, L.Kp, m->fp(L.o_genestat), *link);
-        else TG_LAUNCH(tg_gene_reduce_x, (L.Kp + 63) / 64, 1, 1024, TG_GR_GROUPS * 64 * 2 * 4, m->stream, (const float*)m->fp(L.o_genepart), nrb, L.Kp, m->fp(L.o_genestat), *link);
-    } else if (tg_gene_reduce_is_tall(nrb)) {
-        TG_LAUNCH(tg_gene_reduce_tall, (L.Kp + 15) / 16, 1, 1024, TG_GR_GROUPS * 64 * 2 * 4, m->stream, (const float*)m->fp(L.o_genepart), nrb, L.Kp,
-                  m->fp(L.o_genestat));
-    } else {
-        TG_LAUNCH(tg_gene_reduce, (L.Kp + 63) / 64, 1, 1024, TG_GR_GROUPS * 64 * 2 * 4, m->stream, (const float*)m->fp(L.o_genepart), nrb, L.Kp,
-                  m->fp(L.o_genestat));
-    }
+        if (tall) TG_LAUNCH(tg_gene_reduce_tall_x, shape, m->stream, part, L.grb, L.Kp, m->fp(L.o_genestat), *link);
+        else TG_LAUNCH(tg_gene_reduce_x, shape, m->stream, part, L.grb, L.Kp, m->fp(L.o_genestat), *link);
+    } else if (tall) TG_LAUNCH(tg_gene_reduce_tall, shape, m->stream, part, L.grb, L.Kp, m->fp(L.o_genestat));
+    else TG_LAUNCH(tg_gene_reduce, shape, m->stream, part, L.grb, L.Kp, m->fp(L.o_genestat));
     tg_prof_mark(m, "tg_gene_reduce");
     return TG_OK;
 }
@@ -1025,7 +1042,7 @@ static void tg_loss_args(tg_mapper* m, float* hist_row, TgFinalizeArgs& f, TgEmi
     f.lambda_nb = m->cfg.lambda_neighborhood_g1; f.lambda_ct = m->cfg.lambda_ct_islands; f.T = L.T_ct;
     f.part_out = m->comm ? m->fp(L.o_rowpair) + 2 * (size_t)L.C : nullptr;       // spot shard: this rank's parts of the spot sums
     f.spotpart = nullptr; f.n_spotpart = 0;
-    if (tg_emit_self_ok(m)) { f.spotpart = m->fp(L.o_spotpart); f.n_spotpart = (L.V + TG_RB - 1) / TG_RB; }     // (tg_dghat_emit<SELF> leaves them)
+    if (tg_emit_self_ok(m)) { f.spotpart = m->fp(L.o_spotpart); f.n_spotpart = L.grb; }     // (tg_dghat_emit<SELF> leaves them)
     e.Ghat = m->fp(L.o_Ghat); e.G = m->fp(L.o_Gp); e.coef = m->fp(L.o_coef); e.vcoef = m->fp(L.o_vcoef);
     e.dG = m->ws + L.o_dG;
     // (spot shard: the extra gradient is evaluated for ALL spots; this handle's rows start at its spot offset)
@@ -1035,7 +1052,7 @@ static void tg_loss_args(tg_mapper* m, float* hist_row, TgFinalizeArgs& f, TgEmi
 }
 static bool tg_emit_self_ok(const tg_mapper* m) {      // the emit kernel can derive its coefficients itself (no spatial terms, LDS fits)
     const TgLayout& L = m->L;
-    return !(L.has_nb || L.has_ct || L.has_ac) && L.bands == 1 && (L.Vtot == L.V || m->comm) && (size_t)(2 * L.Kp + 2 * TG_RB) * 4 <= 48 * 1024;
+    return !(L.has_nb || L.has_ct || L.has_ac) && L.bands == 1 && (L.Vtot == L.V || m->comm) && tg_emit_self_fits(L.Kp);
 }
 
 template <class PR>
@@ -1049,31 +1066,33 @@ static int tg_launch_loss(tg_mapper* m, float* hist_row) {
     const bool self = tg_emit_self_ok(m);
     if (self) {
         m->fin_args = f; m->fin_pending = true;
-        const int nrb = (L.V + TG_RB - 1) / TG_RB;
-        int ncol = (512 + nrb - 1) / nrb;                // (column blocks: enough workgroups for two per CU on thin shapes; 1 from 512 spot blocks on)
-        if (ncol > 8) ncol = 8;
-        if (ncol > L.Kp / 128) ncol = L.Kp / 128 > 0 ? L.Kp / 128 : 1;
-        TG_LAUNCH((tg_dghat_emit<PR, false, true>), nrb, ncol, 256, (2 * L.Kp + 2 * TG_RB) * 4, m->stream, e);
+        TG_LAUNCH((tg_dghat_emit<PR, false, true>), tg_dghat_emit_shape(L.V, L.Kp, true, 8), m->stream, e);
         tg_prof_mark(m, "tg_dghat_emit");
         return TG_OK;
     }
     m->fin_pending = false;
     int rcs = tg_launch_spatial_stats(m);
     if (rcs) return rcs;
-    TG_LAUNCH(tg_loss_finalize, 1, 1, 1024, 16 * 5 * 4, m->stream, f);
+    TG_LAUNCH(tg_loss_finalize, tg_shape(1, 1, 1024, 16 * 5 * 4), m->stream, f);
     tg_prof_mark(m, "tg_loss_finalize");
     if ((rcs = tg_launch_spatial_grad(m))) return rcs;
     if (L.has_ac && (rcs = tg_launch_autocorr(m, hist_row))) return rcs;
-    if (e.extra) TG_LAUNCH((tg_dghat_emit<PR, true, false>), (L.V + TG_RB - 1) / TG_RB, 1, 256, 0, m->stream, e);
-    else TG_LAUNCH((tg_dghat_emit<PR, false, false>), (L.V + TG_RB - 1) / TG_RB, 1, 256, 0, m->stream, e);
+    if (e.extra) TG_LAUNCH((tg_dghat_emit<PR, true, false>), tg_dghat_emit_shape(L.V, L.Kp, false, 1), m->stream, e);
+    else TG_LAUNCH((tg_dghat_emit<PR, false, false>), tg_dghat_emit_shape(L.V, L.Kp, false, 1), m->stream, e);
     tg_prof_mark(m, "tg_dghat_emit");
     return TG_OK;
 }
 
 // backward GEMM (X, row-dot partials) over the cell tiles [ct0, ct1) on `stream`; `x_only`: no row dots (they are
 // taken by tg_adam_rowpass)
+// ... over the cell tiles [ct0, ct1) of L.T cells, on tiles of edge `tile`: L.T, or 128 under the 256 layout (L.bwd_T, tg_make_layout)
+struct TgBwdTiles { int ct0, nct, nvt; };
+static TgBwdTiles tg_bwd_tiles(const TgLayout& L, int ct0, int ct1, int tile) {
+    const int f = L.T / tile;
+    return TgBwdTiles{f * ct0, f * (ct1 - ct0), L.Vr / tile};
+}
 template <class PR>
-static TgBwdArgs tg_bwd_args(tg_mapper* m, int ct0, int ct1, int* grid_out, int tile = 0) {      // (ct0, ct1 in tiles of `tile` cells; 0 = L.T)
+static TgBwdArgs tg_bwd_args(tg_mapper* m, const TgBwdTiles& t) {
     const TgLayout& L = m->L;
     TgBwdArgs a;
     a.dG = m->ws + L.o_dG;
@@ -1085,48 +1104,36 @@ static TgBwdArgs tg_bwd_args(tg_mapper* m, int ct0, int ct1, int* grid_out, int 
     a.dens_w = m->cfg.has_d_source ? m->fp(L.o_densw) : nullptr;
     a.part = m->fp(L.o_part);
     a.C = L.C; a.V = L.V; a.Vp = L.Vp; a.Vr = L.Vr; a.Kp = L.Kp; a.nsteps = L.Kp / PR::BKE;
-    const int nct = ct1 - ct0, nvt = tile ? L.Vr / tile : L.nvt;
-    a.ct_offset = ct0;
-    // XCD bands along the longer tile axis when it is long enough to feed 8 XCDs, otherwise a plain linear order
-    if (nct >= 16 && nct >= nvt) { a.map = TgTileMap{1, nct, nvt}; a.map_major_is_cells = 1; }
-    else if (nvt >= 16) { a.map = TgTileMap{1, nvt, nct}; a.map_major_is_cells = 0; }
-    else { a.map = TgTileMap{0, nvt, nct}; a.map_major_is_cells = 0; }
+    a.ct_offset = t.ct0;
+    a.map = tg_bwd_tilemap(t.nct, t.nvt, &a.map_major_is_cells);
     a.lambda_r = m->cfg.lambda_r; a.lambda_l1 = m->cfg.lambda_l1; a.lambda_l2 = m->cfg.lambda_l2;
-    *grid_out = tg_tilemap_grid(a.map);
     return a;
 }
 
 template <class PR>
-static void tg_launch_bwd(tg_mapper* m, tg_stream_t stream, int ct0, int ct1, bool x_only = false, int tile = 0) {
+static void tg_launch_bwd(tg_mapper* m, tg_stream_t stream, int ct0, int ct1, bool x_only = false) {
     const TgLayout& L = m->L;
-    int grid;
-    // (the cached-access variant exists for the single-GPU X-only epilogue only: the row-dot variants serve spot shards and
-    //  very long rows, i.e. big problems, and every GEMM instantiation costs seconds of compile time)
-    // ct0, ct1 count tiles of L.T cells; under the 256 layout the kernel may run on 128^2 tiles (L.bwd_T, see tg_make_layout)
-    if (tile == 0) tile = L.bwd_T;
-    const int f = L.T / tile;
-    const TgBwdArgs a = tg_bwd_args<PR>(m, f * ct0, f * ct1, &grid, tile);
-    tg_with_tile_geo(tile, [&](auto ge) {
+    const TgBwdTiles t = tg_bwd_tiles(L, ct0, ct1, L.bwd_T);      // one step: the tile edge tg_make_layout chose for the backward GEMM
+    const TgBwdArgs a = tg_bwd_args<PR>(m, t);
+    tg_with_tile_geo(L.bwd_T, [&](auto ge) {
         using GE = typename decltype(ge)::type;
-#define TG_BWD_GO(F, R, S) TG_LAUNCH((tg_bwd_kernel<PR, GE, F, R, S>), grid, 1, GE::NT, GE::BWD_LDS_BYTES, stream, a)
-        if (x_only) { if (m->stream_once) TG_BWD_GO(false, false, true); else TG_BWD_GO(false, false, false); }
-        else if (L.full) TG_BWD_GO(true, true, true);
-        else TG_BWD_GO(false, true, true);
-#undef TG_BWD_GO
+        tg_with_bwd_variant(x_only, m->stream_once, L.full, [&](auto fl, auto rd, auto so) {
+            constexpr bool F = decltype(fl)::value, R = decltype(rd)::value, S = decltype(so)::value;
+            TG_LAUNCH((tg_bwd_kernel<PR, GE, F, R, S>), tg_bwd_shape<GE>(t.nct, t.nvt), stream, a);
+        });
     });
 }
 
-static int tg_polling_grid(tg_mapper* m, const void* fn, int nt, int lds, int want);      // (spot-sharded section below)
-static bool tg_grid_strided(const tg_mapper* m);
+static int tg_polling_cap(const tg_mapper* m);      // (spot-sharded section below)
 static void tg_launch_rowsum(tg_mapper* m, tg_stream_t stream, int c0, int c1, const TgPeerLink* link = nullptr) {
     const TgLayout& L = m->L;
     TgRowsumArgs r;
     r.part = m->fp(L.o_part); r.nvt = L.Vr / L.bwd_T; r.C = L.C; r.rowq = m->fp(L.o_rowq); r.np = L.full ? TGP1_N : 1;
     r.c_begin = c0; r.c_end = c1;
     r.xch = 0; r.link.world = 0;
-    int grid = (c1 - c0 + 15) / 16;
-    if (link) { r.xch = 1; r.link = *link; if (tg_grid_strided(m)) grid = tg_polling_grid(m, (const void*)tg_rowsum_parts, 256, 2048, grid); }
-    TG_LAUNCH(tg_rowsum_parts, grid, 1, 256, 2048, stream, r);
+    int max_wg = 0;
+    if (link) { r.xch = 1; r.link = *link; max_wg = tg_polling_cap(m); }
+    TG_LAUNCH(tg_rowsum_parts, tg_rowsum_parts_shape(c1 - c0, max_wg), stream, r);
 }
 
 static void tg_launch_hist_regs(tg_mapper* m, tg_stream_t stream, float* hist_row) {
@@ -1135,7 +1142,7 @@ static void tg_launch_hist_regs(tg_mapper* m, tg_stream_t stream, float* hist_ro
     h.rowq = m->fp(L.o_rowq); h.C = L.C; h.hist = hist_row ? hist_row : m->fp(L.o_scal);
     h.lambda_r = m->cfg.lambda_r; h.lambda_l1 = m->cfg.lambda_l1; h.lambda_l2 = m->cfg.lambda_l2;
     h.constrained = (m->cfg.mode == TG_MODE_CONSTRAINED);
-    TG_LAUNCH(tg_hist_regs, 1, 1, 1024, 64, stream, h);
+    TG_LAUNCH(tg_hist_regs, tg_hist_regs_shape(), stream, h);
 }
 static void tg_hist_regs_marked(tg_mapper* m, float* hist_row) {      // ... on the handle's stream, with its profile mark
     tg_launch_hist_regs(m, m->stream, hist_row);
@@ -1143,6 +1150,7 @@ static void tg_hist_regs_marked(tg_mapper* m, float* hist_row) {      // ... on 
 }
 
 // arguments shared by the update kernels and the row-dot pass, for the cells [c0, c1)
+static bool tg_x16(const tg_mapper* m) { return m->cfg.precision == TG_PREC_BF16 && !m->L.smallc; }   // X in bf16: PrecBF16::X16 (the small-C kernels store X in fp32)
 static TgUpdateArgs tg_update_args(tg_mapper* m, float lr, bool finalize, int c0, int c1) {
     const TgLayout& L = m->L;
     TgUpdateArgs u;
@@ -1156,9 +1164,8 @@ static TgUpdateArgs tg_update_args(tg_mapper* m, float lr, bool finalize, int c0
     u.new_shift = m->fp(L.o_rshift); u.new_invz = m->fp(L.o_rinvz); u.new_mul = m->fp(L.o_rmul); u.new_scale = m->fp(L.o_rscale);
     u.C = L.C; u.V = L.V; u.Vp = L.Vp; u.Vr = L.Vr; u.finalize = finalize ? 1 : 0; u.c_begin = c0; u.c_end = c1;
     u.lambda_r = m->cfg.lambda_r; u.lambda_l1 = m->cfg.lambda_l1; u.lambda_l2 = m->cfg.lambda_l2;
-    const double t = (double)(m->step + 1);
-    u.step_size = (float)((double)lr / (1.0 - pow((double)m->cfg.beta1, t)));
-    u.bc2_sqrt = (float)sqrt(1.0 - pow((double)m->cfg.beta2, t));
+    const TgAdamStep as = tg_adam_step(m->cfg, m->step, lr);
+    u.step_size = as.step_size; u.bc2_sqrt = as.bc2_sqrt;
     u.beta1 = m->cfg.beta1; u.beta2 = m->cfg.beta2; u.eps = m->cfg.eps;
     u.fin_on = 0;
     u.xch = 0; u.link.world = 0;
@@ -1181,11 +1188,11 @@ static int tg_launch_rowdots(tg_mapper* m, float* hist_row) {
 
 // register-resident update of `rows` cell rows (tg_adam_rowpass).  512-thread rows take streaming accesses whatever `stream_once`: with
 // rows that long the cached variant would serve a few hundred cells
-static void tg_launch_rowpass(const TgUpdateArgs& u, bool full, bool x16, bool stream_once, int rows, int V, tg_stream_t stream) {
+static void tg_launch_rowpass(const TgUpdateArgs& u, bool full, bool x16, bool stream_once, int rows, int hist_wg, int V, tg_stream_t stream) {
     tg_with_update_flags(full, x16, stream_once, [&](auto fl, auto xh, auto so) {
         tg_with_row_length(V, [&](auto nq, auto nt) {
             constexpr int NQ = decltype(nq)::value, NT = decltype(nt)::value;
-            TG_LAUNCH((tg_adam_rowpass<decltype(fl)::value, decltype(xh)::value, NQ, NT, (NT == 512 || decltype(so)::value)>), rows, 1, NT, 256, stream, u);
+            TG_LAUNCH((tg_adam_rowpass<decltype(fl)::value, decltype(xh)::value, NQ, NT, (NT == 512 || decltype(so)::value)>), tg_adam_rowpass_shape<NT>(rows, hist_wg), stream, u);
         });
     });
 }
@@ -1198,21 +1205,21 @@ static int tg_launch_update(tg_mapper* m, float lr, bool finalize, tg_stream_t s
     const bool whole = c1 < 0;
     if (whole) { stream = m->stream; c0 = 0; c1 = L.C; }
     TgUpdateArgs u = tg_update_args(m, lr, finalize, c0, c1);
-    const bool x16 = (m->cfg.precision == TG_PREC_BF16) && !L.smallc;     // PrecBF16::X16 (the small-C kernels store X in fp32)
+    const bool x16 = tg_x16(m);
     u.fin_on = 0;
     if (link) { u.xch = 1; u.link = *link; }                              // (fused sharded step: the row pairs are pushed from the kernel's tail)
-    int extra_wg = 0;
-    if (m->fin_pending && whole) { u.fin = m->fin_args; u.fin_on = 1; extra_wg = 1; m->fin_pending = false; }
+    int hist_wg = 0;                                                      // the deferred history row: one extra workgroup
+    if (m->fin_pending && whole) { u.fin = m->fin_args; u.fin_on = 1; hist_wg = 1; m->fin_pending = false; }
     if (rowpass) {
-        tg_launch_rowpass(u, L.full, x16, m->stream_once, c1 - c0 + extra_wg, L.V, stream);
+        tg_launch_rowpass(u, L.full, x16, m->stream_once, c1 - c0, hist_wg, L.V, stream);
         if (whole) tg_prof_mark(m, "tg_adam_rowpass");
         return TG_OK;
     }
     const bool few = (c1 - c0) <= 64 && L.V > 4096;      // a handful of long rows: 1 024 threads per cell
     tg_with_update_flags(L.full, x16, [&](auto fl, auto xh) {
         constexpr bool F = decltype(fl)::value, X = decltype(xh)::value;
-        if (few) TG_LAUNCH((tg_adam_update<F, X, true, 1024>), c1 - c0 + extra_wg, 1, 1024, 512, stream, u);
-        else TG_LAUNCH((tg_adam_update<F, X, true>), c1 - c0 + extra_wg, 1, 256, 128, stream, u);
+        if (few) TG_LAUNCH((tg_adam_update<F, X, true, 1024>), tg_adam_update_shape<1024>(c1 - c0, hist_wg), stream, u);
+        else TG_LAUNCH((tg_adam_update<F, X, true>), tg_adam_update_shape<256>(c1 - c0, hist_wg), stream, u);
     });
     if (whole) tg_prof_mark(m, "tg_adam_update");
     return TG_OK;
@@ -1224,8 +1231,8 @@ static TgSmallArgs tg_small_args(tg_mapper* m, float* hist_row) {
     TgFinalizeArgs f;
     TgEmitArgs e;
     tg_loss_args(m, hist_row, f, e);
-    f.nky = (L.Kp + TG_SC_KC - 1) / TG_SC_KC;     // tg_sc_forward: one block of per-spot statistics per gene chunk
-    f.spotpart = m->fp(L.o_spotpart); f.n_spotpart = (L.V + TG_SC_SB - 1) / TG_SC_SB;
+    f.nky = tg_sc_nch(L.Kp);                      // tg_sc_forward: one block of per-spot statistics per gene chunk
+    f.spotpart = m->fp(L.o_spotpart); f.n_spotpart = tg_sc_nblk(L.V);
     TgSmallArgs a;
     a.M = (const float*)(m->st + L.s_M); a.rmax = m->fp(L.o_rshift); a.rmul = m->fp(L.o_rmul);
     a.Sa = m->fp(L.o_Sa); a.Sx = m->fp(L.o_Sx); a.G = m->fp(L.o_Gp); a.Ghat = m->fp(L.o_Ghat);
@@ -1234,23 +1241,20 @@ static TgSmallArgs tg_small_args(tg_mapper* m, float* hist_row) {
     a.fin = f;
     return a;
 }
-static int tg_small_nblk(const TgLayout& L) { return (L.V + TG_SC_SB - 1) / TG_SC_SB; }        // blocks of 64 spots = rows of genepart
 
 // forward + statistics, backward of one iteration on the small-C kernels; the history scalars are left to the extra workgroup of the
 // update kernel like on the GEMM path (fin_pending)
 static int tg_launch_small(tg_mapper* m, float* hist_row) {
     const TgLayout& L = m->L;
     const TgSmallArgs a = tg_small_args(m, hist_row);
-    const int nblk = tg_small_nblk(L), nch = (L.Kp + TG_SC_KC - 1) / TG_SC_KC;
-#define TG_SC_FWD(CM, VX) TG_LAUNCH((tg_sc_forward<CM, VX>), nblk, nch, TG_SC_KC, tg_sc_lds_fwd(), m->stream, a)
+#define TG_SC_FWD(CM, VX) TG_LAUNCH((tg_sc_forward<CM, VX>), tg_sc_forward_shape(L.V, L.Kp), m->stream, a)
     TG_SC_DISPATCH(L.C, a.want_vox, TG_SC_FWD);
 #undef TG_SC_FWD
     tg_prof_mark(m, "tg_sc_forward");
-    TG_LAUNCH(tg_gene_reduce, (L.Kp + 63) / 64, 1, 1024, TG_GR_GROUPS * 64 * 2 * 4, m->stream, (const float*)m->fp(L.o_genepart), nblk, L.Kp,
-              m->fp(L.o_genestat));
+    TG_LAUNCH(tg_gene_reduce, tg_gene_reduce_shape(L.Kp, false), m->stream, (const float*)m->fp(L.o_genepart), tg_sc_nblk(L.V), L.Kp, m->fp(L.o_genestat));
     tg_prof_mark(m, "tg_gene_reduce");
     m->fin_args = a.fin; m->fin_pending = true;
-#define TG_SC_BWD(CM, VX) TG_LAUNCH((tg_sc_backward<CM>), nblk, 1, TG_SC_KC, tg_sc_lds_bwd(), m->stream, a)
+#define TG_SC_BWD(CM, VX) TG_LAUNCH((tg_sc_backward<CM>), tg_sc_backward_shape(L.V), m->stream, a)
     TG_SC_DISPATCH(L.C, false, TG_SC_BWD);
 #undef TG_SC_BWD
     tg_prof_mark(m, "tg_sc_backward");
@@ -1390,7 +1394,8 @@ extern "C" int tg_batch_create(tg_mapper* const* mappers, int n, void* scratch_d
         if (m->cfg.mode != m0->cfg.mode) return tg_fail(TG_ERR_INVALID, "a batch holds handles of ONE class (Mapper or MapperConstrained)");
         if (m->comm || A.Vtot != A.V || A.bands > 1 || !tg_emit_self_ok(m) || A.V > TG_ROWPASS_MAX_V)
             return tg_fail(TG_ERR_UNSUPPORTED, "mapper %d uses spatial terms, spot shards, the band pipeline, rows longer than %d spots or more genes "
-                           "than the emitter holds (%d padded gene columns, at most 6128: K <= 6015 on 128 tiles, 5887 on 256)", i, TG_ROWPASS_MAX_V, A.Kp);
+                           "than the emitter holds (%d padded gene columns, at most %d: K <= %d on 128 tiles, %d on 256)", i, TG_ROWPASS_MAX_V, A.Kp,
+                           tg_emit_self_kp_max(), tg_emit_self_kp_max() / 128 * 128 - 1, tg_emit_self_kp_max() / 256 * 256 - 1);
         if (m->cfg.beta1 != m0->cfg.beta1 || m->cfg.beta2 != m0->cfg.beta2) return tg_fail(TG_ERR_INVALID, "Adam betas differ inside the batch");
         for (int j = 0; j < i; ++j) if (mappers[j] == m) return tg_fail(TG_ERR_INVALID, "mapper %d appears twice in the batch", i);
     }
@@ -1441,20 +1446,19 @@ static int tg_batch_upload(tg_batch* b, float* const* hist) {
     for (int i = 0; i < n; ++i) {
         tg_mapper* m = b->h[i];
         const TgLayout& L = m->L;
-        int grid;
-        A.fwd[i] = tg_fwd_args<PR>(m, -1, nullptr, false, &grid);
+        A.fwd[i] = tg_fwd_args<PR>(m, -1, nullptr, false);
         A.ghat[i] = tg_ghat_args(m, false);
-        A.gene[i] = TgGeneReduceArgs{m->fp(L.o_genepart), (L.V + TG_RB - 1) / TG_RB, L.Kp, m->fp(L.o_genestat)};
+        A.gene[i] = TgGeneReduceArgs{m->fp(L.o_genepart), L.grb, L.Kp, m->fp(L.o_genestat)};
         TgFinalizeArgs f;
         tg_loss_args(m, nullptr, f, A.emit[i]);
         f.hist = hist ? hist[i] : nullptr;                      // BASE of the mapping's history (row offset: TgStepVar)
         A.emit[i].fin = f;
-        A.bwd[i] = tg_bwd_args<PR>(m, 0, L.nct, &grid);
+        A.bwd[i] = tg_bwd_args<PR>(m, tg_bwd_tiles(L, 0, L.nct, L.T));      // (on L.T tiles: see tg_batch_step_impl)
         if (L.smallc) {                                             // clusters mode: tg_sc_forward / tg_sc_backward take the place of the GEMMs
             A.small[i] = tg_small_args(m, nullptr);
             A.small[i].fin.hist = f.hist;
             f = A.small[i].fin;                                     // (one block of per-spot statistics: nky = 1)
-            A.gene[i].nrb = tg_small_nblk(L);
+            A.gene[i].nrb = tg_sc_nblk(L.V);
         }
         A.upd[i] = tg_update_args(m, 0.f, !constrained, 0, L.C);    // (MapperConstrained: tg_merge_stats folds the NEW filter in afterwards)
         A.upd[i].fin = f; A.upd[i].fin_on = 1;
@@ -1484,13 +1488,11 @@ static int tg_batch_step_impl(tg_batch* b, int n_steps, float lr, float* const* 
     tg_mapper* m0 = b->h[0];
     const TgLayout& L = m0->L;
     tg_stream_t s = m0->stream;
-    const int nrb = (L.V + TG_RB - 1) / TG_RB;
-    const bool x16 = (m0->cfg.precision == TG_PREC_BF16) && !L.smallc;
-    int gf, gb;
-    (void)tg_fwd_args<PR>(m0, -1, nullptr, false, &gf);
-    (void)tg_bwd_args<PR>(m0, 0, L.nct, &gb);
+    const bool x16 = tg_x16(m0);
+    // The backward GEMM by the layout's tile edge L.T, like its arguments (tg_batch_upload), not by L.bwd_T as tg_launch_bwd: a batch ignores
+    // a tg_config.bwd_tile of 128 under the 256 layout.  The automatic choice cannot differ: it needs the row-dot epilogue.
+    const TgBwdTiles bt = tg_bwd_tiles(L, 0, L.nct, L.T);
     const TgBatchArrays A = tg_batch_arrays(b->dev, n);
-    const int nblk = tg_small_nblk(L), sc_nch = (L.Kp + TG_SC_KC - 1) / TG_SC_KC;
     const bool want_vox = (m0->cfg.lambda_g2 != 0.f);
     const int NG = b->n_groups, n_all = n;
     if (NG > 1) {                                    // fork: the groups' streams start behind everything already on the handles' stream
@@ -1503,47 +1505,44 @@ static int tg_batch_step_impl(tg_batch* b, int n_steps, float lr, float* const* 
         tg_stream_t s = grp == 0 ? m0->stream : b->sub[grp - 1];
         const TgUpdateArgs* a_up = A.upd + z0; const TgSmallArgs* a_sm = A.small + z0;
         if (L.smallc) {
-#define TG_SC_FWD_B(CM, VX) TG_LAUNCH3((tg_sc_forward_b<CM, VX>), nblk, sc_nch, n, TG_SC_KC, tg_sc_lds_fwd(), s, a_sm)
+#define TG_SC_FWD_B(CM, VX) TG_LAUNCH_Z((tg_sc_forward_b<CM, VX>), tg_sc_forward_shape(L.V, L.Kp), n, s, a_sm)
             TG_SC_DISPATCH(L.C, want_vox, TG_SC_FWD_B);
 #undef TG_SC_FWD_B
-            TG_LAUNCH3(tg_gene_reduce_b, (L.Kp + 63) / 64, 1, n, 1024, TG_GR_GROUPS * 64 * 2 * 4, s, A.gene + z0);
-#define TG_SC_BWD_B(CM, VX) TG_LAUNCH3((tg_sc_backward_b<CM>), nblk, 1, n, TG_SC_KC, tg_sc_lds_bwd(), s, a_sm)
+            TG_LAUNCH_Z(tg_gene_reduce_b, tg_gene_reduce_shape(L.Kp, false), n, s, A.gene + z0);
+#define TG_SC_BWD_B(CM, VX) TG_LAUNCH_Z((tg_sc_backward_b<CM>), tg_sc_backward_shape(L.V), n, s, a_sm)
             TG_SC_DISPATCH(L.C, false, TG_SC_BWD_B);
 #undef TG_SC_BWD_B
         } else {
             tg_with_fwd_geo<PR>(L, [&](auto ge) {
                 using GE = typename decltype(ge)::type;
-                TG_LAUNCH3((tg_fwd_kernel_b<PR, GE>), gf, 1, n, GE::NT, GE::LDS_BYTES, s, A.fwd + z0);
+                TG_LAUNCH_Z((tg_fwd_kernel_b<PR, GE>), tg_fwd_shape<GE>(tg_fwd_nvt(L), tg_fwd_nkt(L), L.fwd_units), n, s, A.fwd + z0);
             });
-            TG_LAUNCH3(tg_ghat_reduce_b, nrb, (L.Kp + TG_GH_COLS - 1) / TG_GH_COLS, n, 256, 4 * 64 * 2 * 16, s, A.ghat + z0);
-            if (tg_gene_reduce_is_tall(nrb)) {      // no batched twin, and another order of the sums: the solo kernel, once per mapping
+            TG_LAUNCH_Z(tg_ghat_reduce_b, tg_ghat_reduce_shape(L.V, L.Kp), n, s, A.ghat + z0);
+            if (tg_gene_reduce_is_tall(L.grb)) {      // no batched twin, and another order of the sums: the solo kernel, once per mapping
                 for (int i = z0; i < z0 + n; ++i)
-                    TG_LAUNCH(tg_gene_reduce_tall, (L.Kp + 15) / 16, 1, 1024, TG_GR_GROUPS * 64 * 2 * 4, s, (const float*)b->h[i]->fp(b->h[i]->L.o_genepart), nrb,
+                    TG_LAUNCH(tg_gene_reduce_tall, tg_gene_reduce_shape(L.Kp, true), s, (const float*)b->h[i]->fp(b->h[i]->L.o_genepart), L.grb,
                               L.Kp, b->h[i]->fp(b->h[i]->L.o_genestat));
-            } else TG_LAUNCH3(tg_gene_reduce_b, (L.Kp + 63) / 64, 1, n, 1024, TG_GR_GROUPS * 64 * 2 * 4, s, A.gene + z0);
-            TG_LAUNCH3((tg_dghat_emit_b<PR>), nrb, 1, n, 256, (2 * L.Kp + 2 * TG_RB) * 4, s, A.emit + z0);
-            // By the layout's tile edge L.T, like the arguments (tg_bwd_args with tile 0), not by L.bwd_T as tg_launch_bwd: a batch ignores
-            // a tg_config.bwd_tile of 128 under the 256 layout.  The automatic choice cannot differ: it needs the row-dot epilogue.
+            } else TG_LAUNCH_Z(tg_gene_reduce_b, tg_gene_reduce_shape(L.Kp, false), n, s, A.gene + z0);
+            TG_LAUNCH_Z((tg_dghat_emit_b<PR>), tg_dghat_emit_shape(L.V, L.Kp, true, 1), n, s, A.emit + z0);
             tg_with_tile_geo(L.T, [&](auto ge) {
                 using GE = typename decltype(ge)::type;
-                TG_LAUNCH3((tg_bwd_kernel_b<PR, GE>), gb, 1, n, GE::NT, GE::BWD_LDS_BYTES, s, A.bwd + z0);
+                TG_LAUNCH_Z((tg_bwd_kernel_b<PR, GE>), tg_bwd_shape<GE>(bt.nct, bt.nvt), n, s, A.bwd + z0);
             });
         }
-        const double t = (double)(m0->step + 1);
+        const TgAdamStep as = tg_adam_step(m0->cfg, m0->step, lr);
         TgStepVar var;
-        var.step_size = (float)((double)lr / (1.0 - pow((double)m0->cfg.beta1, t)));
-        var.bc2_sqrt = (float)sqrt(1.0 - pow((double)m0->cfg.beta2, t));
+        var.step_size = as.step_size; var.bc2_sqrt = as.bc2_sqrt;
         var.hist_row = hist ? (long long)(first_row + it) : -1;
         tg_with_update_flags(L.full, x16, [&](auto fl, auto xh) {      // (a batch never streams: tg_adam_rowpass_b)
             tg_with_row_length(L.V, [&](auto nq, auto nt) {
                 constexpr int NQ = decltype(nq)::value, NT = decltype(nt)::value;
-                TG_LAUNCH3((tg_adam_rowpass_b<decltype(fl)::value, decltype(xh)::value, NQ, NT>), L.C + 1, 1, n, NT, 256, s, a_up, var);
+                TG_LAUNCH_Z((tg_adam_rowpass_b<decltype(fl)::value, decltype(xh)::value, NQ, NT>), tg_adam_rowpass_shape<NT>(L.C, 1), n, s, a_up, var);
             });
         });
-        if (L.full) TG_LAUNCH3(tg_hist_regs_b, 1, 1, n, 1024, 64, s, A.hreg + z0, var);
+        if (L.full) TG_LAUNCH_Z(tg_hist_regs_b, tg_hist_regs_shape(), n, s, A.hreg + z0, var);
         if (m0->cfg.mode == TG_MODE_CONSTRAINED) {      // Adam on the filters, then the new filters folded into the forward row constants
-            TG_LAUNCH3(tg_filter_kernel_b, 1, 1, n, 1024, 64, s, A.filt + z0, var, A.scr + z0);
-            TG_LAUNCH3(tg_merge_stats_b, (L.C + 255) / 256, 1, n, 256, 0, s, A.merge + z0);
+            TG_LAUNCH_Z(tg_filter_kernel_b, tg_filter_shape(), n, s, A.filt + z0, var, A.scr + z0);
+            TG_LAUNCH_Z(tg_merge_stats_b, tg_merge_stats_shape(L.C), n, s, A.merge + z0);
         }
       }
         for (int i = 0; i < n_all; ++i) b->h[i]->step += 1;
@@ -1794,7 +1793,7 @@ static int tg_peer_exchange_go(tg_comm* c, tg_stream_t stream, const float* send
         c->seq += 1;
         a.seq = c->seq; a.slot = (int)(c->seq & 1u);
         a.send = send + off; a.recv = recv + off; a.n = piece; a.gather = gather; a.ld = n; a.timeout_ticks = c->timeout_ticks;
-        TG_LAUNCH(tg_peer_exchange, (piece + TG_PEER_CHUNK - 1) / TG_PEER_CHUNK, 1, 256, 0, stream, a);
+        TG_LAUNCH(tg_peer_exchange, tg_shape((piece + TG_PEER_CHUNK - 1) / TG_PEER_CHUNK, 1, 256, 0), stream, a);
     }
     return tg_launch_failed() ? tg_launch_status() : TG_OK;
 }
@@ -1851,29 +1850,17 @@ static int tg_exchange_row_stats(tg_mapper* m, float* hist_row) {
 // (one workgroup per row: the dispatcher starts them in order).  Ranks that SHARE a device (the one-GPU tests; tg_comm_peer_create_stepped's
 // `colocated`): a waiting kernel must leave the device to the kernels of the ranks it waits for -- half of the CUs divided by the ranks,
 // one workgroup each, all co-resident, walking their rows with a grid stride.
-static int tg_polling_grid(tg_mapper* m, const void* fn, int nt, int lds, int want) {
-    int g;
+// The most workgroups such a kernel may launch (the shape functions' `max_wg`, tg_capped_grid); 0: no cap.
+static int tg_polling_cap(const tg_mapper* m) {
 #ifdef TG_SIM
-    (void)fn; (void)nt; (void)lds;
-    g = 3;                                                   // (a few rows per workgroup: the grid-stride walk gets exercised)
+    (void)m;
+    return 3;                                                // (the emulator always walks, a few rows per workgroup: the loop is what needs testing there)
 #else
-    static thread_local std::map<const void*, int> per_cu_of;
+    const int col = m->comm->colocated;
+    if (col <= 1) return 0;
     static thread_local int cus = 0;
     if (!cus) { int dev = 0; (void)hipGetDevice(&dev); if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 64; }
-    int& per_cu = per_cu_of[fn];
-    if (!per_cu) { if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, nt, (size_t)lds) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; } }
-    const int col = m->comm ? m->comm->colocated : 1;
-    g = col > 1 ? cus / (2 * col) : cus * per_cu;
-#endif
-    if (g < 1) g = 1;
-    return g < want ? g : want;
-}
-
-static bool tg_grid_strided(const tg_mapper* m) {
-#ifdef TG_SIM
-    (void)m; return true;                                    // (the emulator always walks: the loop is what needs testing there)
-#else
-    return m->comm->colocated > 1;
+    return cus / (2 * col) < 1 ? 1 : cus / (2 * col);
 #endif
 }
 
@@ -1893,9 +1880,7 @@ static TgPeerLink tg_step_link(tg_mapper* m) {
 static int tg_merge_fused(tg_mapper* m, float* hist_row, const TgPeerLink& link) {
     const TgLayout& L = m->L;
     const TgMergeArgs a = tg_merge_args(m, nullptr, m->comm->world, /*finalize=*/true, /*want_pair=*/false, hist_row, m->comm->rank);
-    const int want = (L.C + 255) / 256;
-    const int grid = tg_grid_strided(m) ? tg_polling_grid(m, (const void*)tg_merge_stats_x, 256, 0, want) : want;
-    TG_LAUNCH(tg_merge_stats_x, grid, 1, 256, 0, m->stream, a, link);
+    TG_LAUNCH(tg_merge_stats_x, tg_merge_stats_shape(L.C, tg_polling_cap(m)), m->stream, a, link);
     tg_prof_mark(m, "tg_merge_stats");
     TG_LAUNCH_CK();
     return TG_OK;
@@ -2011,7 +1996,7 @@ extern "C" int tg_mapper_result(tg_mapper* m, float* P_out_dev, float* F_out_dev
     if (!P_out_dev && !F_out_dev) return tg_fail(TG_ERR_INVALID, "P_out is NULL");
     const TgLayout& L = m->L;
     if (P_out_dev)            // (NULL with F_out given: the filter alone, for callers that take the mapping from tg_mapper_result_topk)
-        TG_LAUNCH(tg_softmax_out, L.C, 1, 256, 0, m->stream, (const float*)(m->st + L.s_M),
+        TG_LAUNCH(tg_softmax_out, tg_shape(L.C, 1, 256, 0), m->stream, (const float*)(m->st + L.s_M),
               (const float*)m->fp(L.o_rshift), (const float*)m->fp(L.o_rinvz), L.C, L.V, L.Vp, P_out_dev);
     if (F_out_dev) {
         if (m->cfg.mode != TG_MODE_CONSTRAINED) return tg_fail(TG_ERR_INVALID, "F_out requested from an unconstrained mapper");
@@ -2031,7 +2016,7 @@ extern "C" int tg_mapper_result_topk(tg_mapper* m, int32_t k, float* val_out_dev
     TgTopkArgs a;
     a.M = (const float*)(m->st + L.s_M); a.rshift = m->fp(L.o_rshift); a.rinvz = m->fp(L.o_rinvz);
     a.V = L.V; a.Vp = L.Vp; a.k = k; a.spot_offset = m->cfg.spot_offset; a.val = val_out_dev; a.idx = idx_out_dev;
-    TG_LAUNCH(tg_row_topk, L.C, 1, 256, TG_TOPK_LDS, m->stream, a);
+    TG_LAUNCH(tg_row_topk, tg_shape(L.C, 1, 256, TG_TOPK_LDS), m->stream, a);
     TG_LAUNCH_CK();
     return TG_OK;
 }
@@ -2042,7 +2027,7 @@ extern "C" int tg_topk_merge(const float* val_in_dev, const int32_t* idx_in_dev,
     if (!val_in_dev || !idx_in_dev || !val_out_dev || !idx_out_dev) return tg_fail(TG_ERR_INVALID, "top-k merge: null argument");
     if (n_rows < 1 || n_rows > 0x7fffffffLL || n_in < 1 || ld_in < n_in)
         return tg_fail(TG_ERR_INVALID, "top-k merge: bad lists: rows %lld, entries %d, pitch %lld", (long long)n_rows, n_in, (long long)ld_in);
-    TG_LAUNCH(tg_topk_merge_rows, n_rows, 1, 256, TG_TOPK_LDS, (tg_stream_t)hip_stream, val_in_dev, (const int*)idx_in_dev, n_in, (long long)ld_in,
+    TG_LAUNCH(tg_topk_merge_rows, tg_shape(n_rows, 1, 256, TG_TOPK_LDS), (tg_stream_t)hip_stream, val_in_dev, (const int*)idx_in_dev, n_in, (long long)ld_in,
               k, val_out_dev, (int*)idx_out_dev);
     TG_LAUNCH_CK();
     return TG_OK;
@@ -2067,7 +2052,7 @@ static int tg_project_block(tg_mapper* m, const float* S_blk, long long ld_s, in
     a.Sk = nullptr; a.Cr = L.Cr; a.Kp = L.Kp;
     a.St = m->ws + L.o_StP; a.Cp = L.Cp;
     const size_t n2 = (size_t)L.Kp * (L.Cp / PR::CH);
-    TG_LAUNCH((tg_prep_st<PR>), (n2 + 255) / 256, 1, 256, 0, m->stream, a);
+    TG_LAUNCH((tg_prep_st<PR>), tg_prep_s_shape(n2), m->stream, a);
     return tg_launch_forward<PR>(m, nullptr, -1, m->ws + L.o_StP, unfiltered);
 }
 
@@ -2080,7 +2065,7 @@ extern "C" int tg_mapper_project_genes(tg_mapper* m, const float* S_dev, int64_t
     // adata_map.X is softmax(M) without the filter (mapping_optimizer.py:637): row constants 1/Z and (max + ln Z) log2(e)
     const bool plain = unfiltered && m->cfg.mode == TG_MODE_CONSTRAINED;
     if (plain)
-        TG_LAUNCH(tg_plain_rscale, (L.C + 255) / 256, 1, 256, 0, m->stream, (const float*)m->fp(L.o_rshift),
+        TG_LAUNCH(tg_plain_rscale, tg_shape((L.C + 255) / 256, 1, 256, 0), m->stream, (const float*)m->fp(L.o_rshift),
                   (const float*)m->fp(L.o_rinvz), L.C, m->fp(L.o_rowent));
     for (int k0 = 0; k0 < n_genes; k0 += L.K) {
         const int kc = (n_genes - k0 < L.K) ? n_genes - k0 : L.K;
@@ -2100,7 +2085,7 @@ extern "C" int tg_csr_columns_to_dense(const int64_t* indptr_dev, const int32_t*
     if (!indptr_dev || !indices_dev || !data_dev || !out_dev) return tg_fail(TG_ERR_INVALID, "null argument");
     if (n_rows < 1 || n_cols < 1 || col0 < 0 || ld_out < n_cols) return tg_fail(TG_ERR_INVALID, "bad block: rows %lld, columns %d at %d, pitch %lld",
                                                                                  (long long)n_rows, n_cols, col0, (long long)ld_out);
-    TG_LAUNCH(tg_csr_cols_to_dense, n_rows, 1, 256, 0, (tg_stream_t)hip_stream, (const long long*)indptr_dev, (const int*)indices_dev, data_dev,
+    TG_LAUNCH(tg_csr_cols_to_dense, tg_shape(n_rows, 1, 256, 0), (tg_stream_t)hip_stream, (const long long*)indptr_dev, (const int*)indices_dev, data_dev,
               col0, n_cols, out_dev, (long long)ld_out);
     TG_LAUNCH_CK();
     return TG_OK;
@@ -2141,12 +2126,12 @@ extern "C" int tg_sparse_map_build(const int64_t* indptr_dev, const int32_t* ind
     float* tval = (float*)(ws + L.o_tval);
     const long long entry_grid = (nnz + 255) / 256;
     if (n_spots > 0) TG_CK(tg_memset(cnt, 0, 4 * (size_t)n_spots, s));
-    if (nnz > 0) TG_LAUNCH(tg_sp_count, entry_grid, 1, 256, 0, s, (const int*)indices_dev, (long long)nnz, cnt);
-    TG_LAUNCH(tg_sp_scan, 1, 1, 1024, 1024 * 8, s, cnt, (long long)n_spots, spot_ptr);
+    if (nnz > 0) TG_LAUNCH(tg_sp_count, tg_shape(entry_grid, 1, 256, 0), s, (const int*)indices_dev, (long long)nnz, cnt);
+    TG_LAUNCH(tg_sp_scan, tg_shape(1, 1, 1024, 1024 * 8), s, cnt, (long long)n_spots, spot_ptr);
     if (nnz > 0) {
-        TG_LAUNCH(tg_sp_scatter, entry_grid, 1, 256, 0, s, (const long long*)indptr_dev, (const int*)indices_dev, data_dev, (int)n_cells,
+        TG_LAUNCH(tg_sp_scatter, tg_shape(entry_grid, 1, 256, 0), s, (const long long*)indptr_dev, (const int*)indices_dev, data_dev, (int)n_cells,
                   (long long)nnz, (const long long*)spot_ptr, cnt, tcell, tval);
-        TG_LAUNCH(tg_sp_order, n_spots, 1, 256, TG_SP_TILE * 4, s, (const long long*)spot_ptr, (const int*)tcell, (const float*)tval,
+        TG_LAUNCH(tg_sp_order, tg_shape(n_spots, 1, 256, TG_SP_TILE * 4), s, (const long long*)spot_ptr, (const int*)tcell, (const float*)tval,
                   (int*)(ws + L.o_cell), (float*)(ws + L.o_val));
     }
     TG_LAUNCH_CK();
@@ -2172,8 +2157,9 @@ extern "C" int tg_sparse_map_project(const void* workspace_dev, int64_t n_cells,
     const long long per_launch = (1LL << 30) / ntiles;                                           // spots per launch: grid <= 2^30
     for (long long v0 = 0; v0 < n_spots; v0 += per_launch) {
         a.v0 = (int)v0; a.nv = (int)(n_spots - v0 < per_launch ? n_spots - v0 : per_launch);
-        if (vec) TG_LAUNCH((tg_sp_project<true>), ntiles * a.nv, 1, 256, 0, (tg_stream_t)hip_stream, a);
-        else TG_LAUNCH((tg_sp_project<false>), ntiles * a.nv, 1, 256, 0, (tg_stream_t)hip_stream, a);
+        const TgShape tiles = tg_shape(ntiles * a.nv, 1, 256, 0);
+        if (vec) TG_LAUNCH((tg_sp_project<true>), tiles, (tg_stream_t)hip_stream, a);
+        else TG_LAUNCH((tg_sp_project<false>), tiles, (tg_stream_t)hip_stream, a);
     }
     TG_LAUNCH_CK();
     return TG_OK;
@@ -2184,7 +2170,7 @@ extern "C" int tg_csr_gather_columns(const int64_t* indptr_dev, const int32_t* i
     if (!indptr_dev || !indices_dev || !data_dev || !colmap_dev || !out_dev) return tg_fail(TG_ERR_INVALID, "null argument");
     if (n_rows < 1 || n_out_cols < 1 || ld_out < n_out_cols) return tg_fail(TG_ERR_INVALID, "bad gather: rows %lld, columns %d, pitch %lld",
                                                                             (long long)n_rows, n_out_cols, (long long)ld_out);
-    TG_LAUNCH(tg_csr_gather_cols, n_rows, 1, 256, 0, (tg_stream_t)hip_stream, (const long long*)indptr_dev, (const int*)indices_dev, data_dev,
+    TG_LAUNCH(tg_csr_gather_cols, tg_shape(n_rows, 1, 256, 0), (tg_stream_t)hip_stream, (const long long*)indptr_dev, (const int*)indices_dev, data_dev,
               (const int*)colmap_dev, n_out_cols, out_dev, (long long)ld_out);
     TG_LAUNCH_CK();
     return TG_OK;
@@ -2194,9 +2180,9 @@ extern "C" int tg_row_sums(const float* X_dev, int64_t ld, int32_t n_cols, const
                            float* out_dev, int32_t normalize, void* hip_stream) {
     if (!out_dev || (!X_dev && !(indptr_dev && data_dev))) return tg_fail(TG_ERR_INVALID, "null argument");
     if (n_rows < 1 || (X_dev && (n_cols < 1 || ld < n_cols))) return tg_fail(TG_ERR_INVALID, "bad matrix shape");
-    TG_LAUNCH(tg_row_sums, (n_rows + 3) / 4, 1, 256, 4 * 64 * 8, (tg_stream_t)hip_stream, X_dev, (long long)ld, n_cols,
+    TG_LAUNCH(tg_row_sums, tg_shape((n_rows + 3) / 4, 1, 256, 4 * 64 * 8), (tg_stream_t)hip_stream, X_dev, (long long)ld, n_cols,
               X_dev ? (const long long*)nullptr : (const long long*)indptr_dev, data_dev, (long long)n_rows, out_dev);
-    if (normalize) TG_LAUNCH(tg_normalize_total, 1, 1, 1024, 1024 * 8, (tg_stream_t)hip_stream, out_dev, (long long)n_rows);
+    if (normalize) TG_LAUNCH(tg_normalize_total, tg_shape(1, 1, 1024, 1024 * 8), (tg_stream_t)hip_stream, out_dev, (long long)n_rows);
     TG_LAUNCH_CK();
     return TG_OK;
 }
@@ -2209,7 +2195,7 @@ extern "C" int tg_init_logits_normal(float* out_dev, int64_t n_rows, int64_t n_c
                        (long long)col0, (long long)n_cols_total);
     const long long quads = n_rows * ((n_cols + 3) / 4);
     const int grid = (int)(quads / 256 + 1 < 16384 ? quads / 256 + 1 : 16384);
-    TG_LAUNCH(tg_init_normal, grid, 1, 256, 0, (tg_stream_t)hip_stream, out_dev, (long long)n_rows, (long long)n_cols, (long long)ld,
+    TG_LAUNCH(tg_init_normal, tg_shape(grid, 1, 256, 0), (tg_stream_t)hip_stream, out_dev, (long long)n_rows, (long long)n_cols, (long long)ld,
               (unsigned long long)seed, (long long)col0, (long long)n_cols_total);
     TG_LAUNCH_CK();
     return TG_OK;
@@ -2220,7 +2206,7 @@ extern "C" int tg_cluster_aggregate(const float* X_dev, int64_t ld, int32_t n_co
                                     void* hip_stream) {
     if (!X_dev || !member_indptr_dev || !member_rows_dev || !out_dev) return tg_fail(TG_ERR_INVALID, "null argument");
     if (n_clusters < 1 || n_cols < 1 || ld < n_cols || ld_out < n_cols) return tg_fail(TG_ERR_INVALID, "bad aggregation shape");
-    TG_LAUNCH(tg_cluster_sums, n_clusters, (n_cols + 255) / 256, 256, 0, (tg_stream_t)hip_stream, X_dev, (long long)ld, n_cols,
+    TG_LAUNCH(tg_cluster_sums, tg_shape(n_clusters, (n_cols + 255) / 256, 256, 0), (tg_stream_t)hip_stream, X_dev, (long long)ld, n_cols,
               (const int*)member_indptr_dev, (const int*)member_rows_dev, mean, out_dev, (long long)ld_out);
     TG_LAUNCH_CK();
     return TG_OK;
@@ -2240,9 +2226,10 @@ extern "C" int tg_mapper_validate(tg_mapper* m, float* out4_dev) {
     if (rc) return rc;
     if ((rc = tg_launch_ghat_stats(m, true))) return rc;
     if (m->comm && (rc = tg_exchange_all_reduce(m, m->fp(L.o_genestat), (size_t)2 * L.Kp))) return rc;      // per-gene sums over all spots
-    TG_LAUNCH(tg_row_entropy, L.C, 1, 256, 64, m->stream, (const float*)(m->st + L.s_M), (const float*)m->fp(L.o_rshift),
+    TG_LAUNCH(tg_row_entropy, tg_shape(L.C, 1, 256, 64), m->stream, (const float*)(m->st + L.s_M), (const float*)m->fp(L.o_rshift),
               (const float*)m->fp(L.o_rinvz), L.V, L.Vp, m->fp(L.o_rowent));
     TgValArgs a;
+    const TgShape fin = tg_shape(1, 1, 1024, 64);
     a.genestat = m->fp(L.o_genestat); a.gnorm2 = m->fp(L.o_gnorm2); a.gfrac = m->fp(L.o_gfrac);
     a.voxstat = m->fp(L.o_voxstat); a.nky = (L.Kp + TG_GH_COLS - 1) / TG_GH_COLS; a.vnorm2 = m->fp(L.o_vnorm2); a.rowent = m->fp(L.o_rowent);
     a.out = out4_dev; a.K = L.K; a.Kp = L.Kp; a.V = L.V; a.Vr = L.Vr; a.C = L.C;
@@ -2251,11 +2238,11 @@ extern "C" int tg_mapper_validate(tg_mapper* m, float* out4_dev) {
         // the sums over spots, per rank -> all-reduce -> every rank finishes with the same numbers.  Scratch: the gene coefficient
         // buffer [2][Kp] (rewritten by the loss kernels of the next step); Kp >= 128, so 64 + Kp floats fit.
         a.part = m->fp(L.o_coef); a.partial = 1;
-        TG_LAUNCH(tg_val_finalize, 1, 1, 1024, 64, m->stream, a);
+        TG_LAUNCH(tg_val_finalize, fin, m->stream, a);
         if ((rc = tg_exchange_all_reduce(m, a.part, (size_t)64 + L.Kp))) return rc;
         a.partial = 0;
     }
-    TG_LAUNCH(tg_val_finalize, 1, 1, 1024, 64, m->stream, a);
+    TG_LAUNCH(tg_val_finalize, fin, m->stream, a);
     TG_LAUNCH_CK();
     return TG_OK;
 }
@@ -2351,7 +2338,7 @@ extern "C" int tg_debug_fwd_decomposition(const tg_config* cfg, int* out) {
     TgLayout L;
     const int rc = tg_make_layout(cfg, &L);
     if (rc != TG_OK) return rc;
-    out[0] = L.fwd_units; out[1] = L.fwd_wide ? L.Kp / 512 : L.nkt; out[2] = L.fwd_wide ? L.Vr / 128 : L.nvt; out[3] = L.Cp / L.BKE;
+    out[0] = L.fwd_units; out[1] = tg_fwd_nkt(L); out[2] = tg_fwd_nvt(L); out[3] = L.Cp / L.BKE;
     return TG_OK;
 }
 // Host replay of the forward launch of a configuration (no device needed): every workgroup of the grid walks its segments through the
@@ -2363,8 +2350,8 @@ extern "C" int tg_debug_fwd_cover(const tg_config* cfg, long long* out) {
     const int rc = tg_make_layout(cfg, &L);
     if (rc != TG_OK) return rc;
     if (L.smallc || L.bands > 1) return tg_fail(TG_ERR_INVALID, "tg_debug_fwd_cover: this configuration does not launch the decomposed forward GEMM");
-    const int nvt = L.fwd_wide ? L.Vr / 128 : L.nvt, nkt = L.fwd_wide ? L.Kp / 512 : L.nkt, nsteps = L.Cp / L.BKE, units = L.fwd_units;
-    const int grid = (units % nvt == 0) ? tg_fwd_grid(nvt, nkt, units / nvt) : tg_fwd_units_grid(units, nkt);
+    const int nvt = tg_fwd_nvt(L), nkt = tg_fwd_nkt(L), nsteps = L.Cp / L.BKE, units = L.fwd_units;
+    const int grid = (int)tg_fwd_shape<TgGeoSmall>(nvt, nkt, units).gx;        // (the grid is the same on every geometry)
     const long long G = (long long)nvt * nsteps;
     std::vector<unsigned char> taken((size_t)nvt * nkt * nsteps, 0), slot((size_t)nvt * nkt * L.nsplit, 0);
     long long working = 0, lo = -1, hi = 0, most_seg = 0;
@@ -2406,7 +2393,7 @@ extern "C" int tg_debug_sparse_map_layout(int64_t n_spots, int64_t nnz, int64_t 
 // out[0..n) = sqrt(a), out[n..2n) = a / b, out[2n..3n) = a / bc (device arrays; enqueued on hip_stream)
 extern "C" int tg_debug_adam_math(const float* a_dev, const float* b_dev, float bc, float* out_dev, long long n, void* hip_stream) {
     if (!a_dev || !b_dev || !out_dev || n < 1) return tg_fail(TG_ERR_INVALID, "null argument");
-    TG_LAUNCH(tg_adam_math_probe, (n + 255) / 256, 1, 256, 0, (tg_stream_t)hip_stream, a_dev, b_dev, bc, out_dev, n);
+    TG_LAUNCH(tg_adam_math_probe, tg_shape((n + 255) / 256, 1, 256, 0), (tg_stream_t)hip_stream, a_dev, b_dev, bc, out_dev, n);
     TG_LAUNCH_CK();
     return TG_OK;
 }

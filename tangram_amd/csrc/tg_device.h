@@ -5,6 +5,7 @@
 //   -DTG_SIM  host clang + tests/hipsim/hipsim.h: test-only emulation used by the CPU test-suite
 //             (the authoring container has no GPU).  Nothing in the product loads a TG_SIM build.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include <type_traits>
 
@@ -12,6 +13,14 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+
+// Launch shape of a kernel (host side): grid x / y, threads per workgroup, dynamic LDS bytes.  A kernel launched from more than one
+// site, or with a _b / _x / _tall sibling, has ONE function tg_<kernel>_shape next to its body -- where its launch bounds and its carve
+// of TG_LDS_DECL are written -- and every launch site takes the shape from there (TG_LAUNCH, tg_capi.hip).
+struct TgShape { unsigned gx, gy, block; size_t lds; };
+static inline TgShape tg_shape(unsigned long long gx, unsigned long long gy, unsigned block, size_t lds) {
+    return TgShape{(unsigned)gx, (unsigned)gy, block, lds};
+}
 
 #ifdef TG_SIM
 // ------------------------------------------------------------------------------------------

@@ -246,6 +246,11 @@ TG_HD bool tg_fwd_map(int b, int nvt, int nkt, int nsplit, int& vt, int& kt, int
     vt = unit % nvt;
     return unit < nvt * nsplit;
 }
+// tg_fwd_kernel, tg_fwd_kernel_b on geometry GE: a whole pass cut into `units` pieces per gene tile, or (`band`) ONE cell range of every tile
+template <class GE> TG_HD TgShape tg_fwd_shape(int nvt, int nkt, int units, bool band = false) {
+    const int grid = band ? tg_fwd_grid(nvt, nkt, 1) : (units % nvt == 0) ? tg_fwd_grid(nvt, nkt, units / nvt) : tg_fwd_units_grid(units, nkt);
+    return tg_shape(grid, 1, GE::NT, GE::LDS_BYTES);
+}
 
 // The segments of workgroup b, in order: f(spot tile, gene tile, partial slot, first step, one past the last step).  Shared by the
 // kernel and by tg_debug_fwd_cover (host), which replays every workgroup of a grid and checks that each (tile, step) is taken
@@ -472,6 +477,18 @@ TG_DEV void tg_fwd_segment(const TgFwdArgs& a, int vt, int kt, int part_slot, in
 //   update runs as a second, purely streaming kernel (tg_adam_update) on the stored X.
 //   Fragment ownership: lane holds 4 consecutive spots (one float4 of M) for cell c = lane&15.
 // ----------------------------------------------------------------------------------------------
+// workgroup -> tile map of the backward GEMM over nct cell tiles x nvt spot tiles: XCD bands along the longer tile axis when it is long
+// enough to feed 8 XCDs, otherwise a plain linear order
+TG_HD TgTileMap tg_bwd_tilemap(int nct, int nvt, int* major_is_cells) {
+    *major_is_cells = (nct >= 16 && nct >= nvt) ? 1 : 0;
+    if (*major_is_cells) return TgTileMap{1, nct, nvt};
+    return nvt >= 16 ? TgTileMap{1, nvt, nct} : TgTileMap{0, nvt, nct};
+}
+// tg_bwd_kernel, tg_bwd_kernel_b on GE-edge tiles (the tile edge is the caller's: tg_launch_bwd, tg_batch_step_impl in tg_capi.hip)
+template <class GE> TG_HD TgShape tg_bwd_shape(int nct, int nvt) {
+    int major_is_cells;
+    return tg_shape(tg_tilemap_grid(tg_bwd_tilemap(nct, nvt, &major_is_cells)), 1, GE::NT, GE::BWD_LDS_BYTES);
+}
 struct TgBwdArgs {
     const unsigned char* dG;      // A operand [Vr][nsteps][128 B]
     const unsigned char* Sk;      // B operand [Cr][nsteps][128 B]

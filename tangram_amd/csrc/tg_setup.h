@@ -119,6 +119,7 @@ TG_DEV float tg_s_aug(const TgPrepSArgs& a, int c, int k) {
     if (a.ct && k - a.K - 1 < a.T) return a.ct[(size_t)c * a.T + (k - a.K - 1)];
     return 0.f;
 }
+TG_HD TgShape tg_prep_s_shape(size_t chunks) { return tg_shape((chunks + 255) / 256, 1, 256, 0); }      // tg_prep_sk, tg_prep_st: one thread per operand chunk
 template <class PR>
 TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_prep_sk(TgPrepSArgs a) {
     const int nch = a.Kp / PR::CH;

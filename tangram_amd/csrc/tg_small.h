@@ -35,6 +35,11 @@ TG_HD int tg_sc_cm(int C) { return (C + 3) / 4 * 4; }
 #define TG_SC_PP 80            // row pitch (floats) of the P tile in LDS [cluster][spot]: rows 16 banks apart
 TG_HD int tg_sc_lds_fwd() { return (4 * TG_SC_TILE + TG_SC_MAXC * TG_SC_PP + 4 * 2 * TG_SC_SB) * 4; }
 TG_HD int tg_sc_lds_bwd() { return (4 * TG_SC_TILE + TG_SC_MAXC * TG_SC_PP + 4 * 64 * 4 + 2 * TG_SC_SB) * 4; }
+TG_HD int tg_sc_nblk(int V) { return (V + TG_SC_SB - 1) / TG_SC_SB; }                 // blocks of 64 spots = rows of genepart
+TG_HD int tg_sc_nch(int Kp) { return (Kp + TG_SC_KC - 1) / TG_SC_KC; }                // gene chunks = blocks of per-spot statistics
+// tg_sc_forward(_b): (spot blocks, gene chunks); tg_sc_backward(_b): spot blocks
+TG_HD TgShape tg_sc_forward_shape(int V, int Kp) { return tg_shape(tg_sc_nblk(V), tg_sc_nch(Kp), TG_SC_KC, tg_sc_lds_fwd()); }
+TG_HD TgShape tg_sc_backward_shape(int V) { return tg_shape(tg_sc_nblk(V), 1, TG_SC_KC, tg_sc_lds_bwd()); }
 
 // Matrix-core layout of the small-C kernels (v_mfma_f32_16x16x4_f32, exact fp32 products): lane = (grp = lane / 16, ln = lane % 16).
 // A tile of Ghat^T, 16 genes x 16 spots, is  sum_c St[gene][c] P[c][spot]:  A operand a_j = St[kt + ln][4 j + grp], B operand

@@ -23,6 +23,7 @@ struct TgSpmmArgs {
 // takes a CONTIGUOUS band of spots (rows x * V/8 ...), so that a band's gathered rows are shared through that XCD's L2 instead of every
 // XCD streaming the whole matrix; (ii) the non-zeros of a row are taken eight at a time with every gathered row requested before the
 // first is used (the one-at-a-time loop was a chain of ~7 dependent row loads).  Same sums in the same order: same bits.
+TG_HD TgShape tg_spmm_shape(int V) { return tg_shape(V, 1, 256, 0); }          // one workgroup per spot row
 TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_spmm(TgSpmmArgs a) {
     constexpr int U = 8;
     const int nb = gridDim.x, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
@@ -69,6 +70,8 @@ TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_spmm(TgSpmmArgs a) {
     }
 }
 
+// the kernels over blocks of TG_RB spots: tg_colstats, tg_ac_stats1, tg_ac_stats2, tg_ac_refs, tg_ac_grad
+TG_HD TgShape tg_spot_blocks_shape(int V) { return tg_shape(tg_row_blocks(V), 1, 256, 0); }
 // per-gene partial sums over a block of TG_RB spots: (sum A*B, sum A*A)  [second stage: tg_gene_reduce]
 TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_colstats(const float* A, const float* B, int V, int Kp, float* part /*[nrb][2][Kp]*/) {
     const int rb = blockIdx.x, vbeg = rb * TG_RB;
@@ -140,6 +143,7 @@ struct TgAcArgs {
     float lam_getis, lam_moran, lam_geary;
 };
 
+TG_HD TgShape tg_csr_rowsum_shape(int V) { return tg_shape((V + 255) / 256, 1, 256, 0); }
 TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_csr_rowsum(TgCsr W, int V, float* out, int accumulate) {
     const int v = blockIdx.x * 256 + threadIdx.x;
     if (v >= V) return;
@@ -170,6 +174,7 @@ TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_ac_stats1(TgAcArgs a) {
     }
 }
 // deterministic second stage of any [nparts][nstat][Kp] partial array
+TG_HD TgShape tg_stat_reduce_shape(int Kp) { return tg_shape((Kp + 255) / 256, 1, 256, 0); }
 TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_stat_reduce(const float* part, int nparts, int nstat, int Kp, float* out) {
     const int k = blockIdx.x * 256 + threadIdx.x;
     if (k >= Kp) return;

@@ -6,6 +6,7 @@
 //   (cosine_similarity statistics, mapping_optimizer.py:205-206)
 // ----------------------------------------------------------------------------------------------
 #define TG_RB 16   // spots per block in the V x Kp elementwise kernels
+TG_HD int tg_row_blocks(int V) { return (V + TG_RB - 1) / TG_RB; }      // ... and the blocks of V spots: their grid x
 
 struct TgGhatReduceArgs {
     const float* Gpart; int nsplit;
@@ -89,6 +90,8 @@ TG_DEV void tg_ghat_reduce_body(const TgGhatReduceArgs& a) {
         }
     }
 }
+// tg_ghat_reduce, tg_ghat_reduce_b.  LDS: `red`, [4 row groups][64 lanes][2] f32x4
+TG_HD TgShape tg_ghat_reduce_shape(int V, int Kp) { return tg_shape(tg_row_blocks(V), (Kp + TG_GH_COLS - 1) / TG_GH_COLS, 256, 4 * 64 * 2 * 16); }
 
 // K2b: second stage of the per-gene sums (fixed order => deterministic): KX genes x 1024 / KX partial groups per block.
 // (A latency-bound kernel: every thread walks nrb / groups row blocks; with 4 groups it took 29 us at 600 row blocks.  KX = 64:
@@ -132,6 +135,10 @@ TG_DEV void tg_gene_reduce_body(const float* genepart, int nrb, int Kp, float* g
         genestat[Kp + k] = n;
     }
 }
+// many row blocks, e.g. 10 000 spots: tg_gene_reduce_tall(_x), 16 genes x 64 groups per workgroup (another order of the sums)
+TG_HD bool tg_gene_reduce_is_tall(int nrb) { return nrb > 512; }
+// tg_gene_reduce, _x, _b (KX = 64) and tg_gene_reduce_tall, _tall_x (KX = 16).  LDS: `red`, [1024 / KX groups][KX][2] floats
+TG_HD TgShape tg_gene_reduce_shape(int Kp, bool tall) { return tg_shape(tall ? (Kp + 15) / 16 : (Kp + 63) / 64, 1, 1024, TG_GR_GROUPS * 64 * 2 * 4); }
 
 // ----------------------------------------------------------------------------------------------
 // K2c: scalars + gradient coefficients.  One block of 1024 threads.
@@ -329,6 +336,20 @@ struct TgEmitArgs {
 // reduced statistics, into LDS -- they are purely local functions of them.  tg_loss_finalize (one workgroup, ~20 us of
 // dependent latency) then no longer sits between the forward and the backward GEMM: the scalars of the history row are
 // produced by one extra workgroup of the update kernel, off the critical path.  dynamic LDS: (2 Kp + 2 TG_RB) floats.
+// SELF: dynamic LDS bytes of `cf`, [2][Kp] alpha, beta + [2][TG_RB] va, vb.  It must fit the 48 KB a kernel gets without a raised
+// attribute: tg_emit_self_kp_max() padded gene columns at most.
+TG_HD size_t tg_emit_self_lds(int Kp) { return (size_t)(2 * Kp + 2 * TG_RB) * 4; }
+TG_HD bool tg_emit_self_fits(int Kp) { return tg_emit_self_lds(Kp) <= 48 * 1024; }
+TG_HD int tg_emit_self_kp_max() { return (48 * 1024 / 4 - 2 * TG_RB) / 2; }
+// tg_dghat_emit, tg_dghat_emit_b: (blocks of TG_RB spots, column blocks).  `max_col`, the most column blocks -- one step: 8, enough
+// workgroups for two per CU on thin shapes (1 from 512 spot blocks on); a batch: 1, its mappings (blockIdx.z) multiply the workgroups.
+TG_HD TgShape tg_dghat_emit_shape(int V, int Kp, bool self, int max_col) {
+    const int nrb = tg_row_blocks(V);
+    int ncol = (512 + nrb - 1) / nrb;
+    if (ncol > max_col) ncol = max_col;
+    if (ncol > Kp / 128) ncol = Kp / 128 > 0 ? Kp / 128 : 1;
+    return tg_shape(nrb, self ? ncol : 1, 256, self ? tg_emit_self_lds(Kp) : 0);
+}
 template <class PR, bool EXTRA, bool SELF>
 TG_DEV void tg_dghat_emit_body(const TgEmitArgs& a) {
     TG_LDS_DECL;

@@ -123,6 +123,13 @@ TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_adam_math_probe(const float* a, const fl
     out[2 * n + i] = tg_div_by(a[i], bc, 1.f / bc);
 }
 
+// Grid x of a kernel whose workgroups WAIT for pushes of other ranks (tg_rowsum_parts with xch, tg_merge_stats_x): `want` workgroups, or
+// `max_wg` of them walking their rows with a grid stride (ranks that share a device: tg_polling_cap, tg_capi.hip; 0 = no cap)
+TG_HD int tg_capped_grid(int want, int max_wg) { return (max_wg > 0 && max_wg < want) ? max_wg : want; }
+// tg_adam_update<.., NT>: one workgroup per cell row + `hist_wg` (0 / 1) that writes the deferred history row.  LDS: `red`, up to [NT / 64][5] floats
+template <int NT> TG_HD TgShape tg_adam_update_shape(int rows, int hist_wg) { return tg_shape(rows + hist_wg, 1, NT, NT == 1024 ? 512 : 128); }
+// tg_adam_rowpass(_b)<.., NT, ..>: likewise (a batch always launches the history workgroup).  LDS: `red` + `red2`, [NT / 64][TGP1_N + 2] floats at most
+template <int NT> TG_HD TgShape tg_adam_rowpass_shape(int rows, int hist_wg) { return tg_shape(rows + hist_wg, 1, NT, 256); }
 // NT = 256 threads per cell; 1 024 for a handful of long rows (clusters mode beyond 16 384 spots: with 18 workgroups the kernel is
 // one dependent chain of V / (4 NT) trips per thread -- 81 us at 50 000 spots with 256 threads)
 template <bool FULL, bool X16, bool STREAM, int NT = 256>
@@ -362,6 +369,8 @@ struct TgRowsumArgs {
     int xch; TgPeerLink link;  // xch (spot shard, peer transport with a step area): the thread that owns a cell's sum pushes it into every rank's
                                // mailbox and stores the rank-order sum of the world's granules: what an all-reduce after this kernel delivers
 };
+// tg_rowsum_parts: 16 cells per workgroup.  LDS: `red` [16][16] + `loc` [np][16] floats
+TG_HD TgShape tg_rowsum_parts_shape(int cells, int max_wg) { return tg_shape(tg_capped_grid((cells + 15) / 16, max_wg), 1, 256, 2048); }
 // 16 cells x 16 groups of spot tiles per workgroup: a cell's partials p = g, g + 16, ... side by side, then the groups in fixed order
 // (one thread per cell walking all V / 128 partials took 61 us at 50 000 spots and 18 rows of M)
 TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_rowsum_parts(TgRowsumArgs a) {
@@ -369,7 +378,7 @@ TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_rowsum_parts(TgRowsumArgs a) {
     float* red = (float*)tg_lds;                                 // [16][16]
     float* loc = red + 256;                                      // xch: [np][16] this rank's sums of the block's cells
     const int r = threadIdx.x & 15, g = threadIdx.x >> 4;
-    // (a grid-stride walk over the blocks of 16 cells: one trip unless the grid was cut short -- ranks sharing a device, tg_polling_grid)
+    // (a grid-stride walk over the blocks of 16 cells: one trip unless the grid was cut short -- ranks sharing a device, tg_polling_cap)
     for (int blk = blockIdx.x; a.c_begin + blk * 16 < a.c_end; blk += (int)gridDim.x) {
         const int c = a.c_begin + blk * 16 + r;
         for (int q = 0; q < a.np; ++q) {
@@ -400,6 +409,7 @@ TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_rowsum_parts(TgRowsumArgs a) {
 // entropy / L1 / L2 scalars (mapping_optimizer.py:224-231) from the per-row sums -> history row
 struct TgHistRegArgs { const float* rowq; int C; float* hist; float lambda_r, lambda_l1, lambda_l2; int constrained; };
 
+TG_HD TgShape tg_hist_regs_shape() { return tg_shape(1, 1, 1024, 64); }      // tg_hist_regs(_b): one workgroup, one float per wave
 TG_DEV void tg_hist_regs_body(const TgHistRegArgs& a) {
     TG_LDS_DECL;
     float* red = (float*)tg_lds;
@@ -514,6 +524,7 @@ TG_DEV void tg_filter_body(const TgFilterArgs& a) {
     const float fsum_new = tg_block_sum_1024(fs, red);          // (its barriers also order every thread's read of fsum above before this write)
     if (t == 0) a.fsum[0] = fsum_new;
 }
+TG_HD TgShape tg_filter_shape() { return tg_shape(1, 1, 1024, 64); }         // tg_filter_kernel(_b): one workgroup, one float per wave
 TG_KERNEL void TG_LAUNCH_BOUNDS(1024) tg_filter_kernel(TgFilterArgs a) { tg_filter_body(a); }
 // batched (tg_batch of MapperConstrained handles): Adam step constants and the history row travel by value
 TG_KERNEL void TG_LAUNCH_BOUNDS(1024) tg_filter_kernel_b(const TgFilterArgs* argv, TgStepVar var, float* const* scratch_rows) {
@@ -557,7 +568,7 @@ TG_DEV void tg_merge_stats_body(const TgMergeArgs& a, const TgPeerLink* link = n
             if (tg_sys_load_u32((const unsigned*)link->box[link->rank]) != 0u)
                 for (int i = 0; i < TGH_NTERMS; ++i) a.hist[i] = __builtin_nanf("");
         }
-        // (a grid-stride walk: ranks that SHARE a device -- the one-GPU tests -- poll with few workgroups, see tg_polling_grid)
+        // (a grid-stride walk: ranks that SHARE a device -- the one-GPU tests -- poll with few workgroups, see tg_polling_cap)
         for (; c < a.C; c += (int)gridDim.x * 256) {
         float pm[TG_PEER_MAX], pz[TG_PEER_MAX];
         float mx = TG_NEG_BIG;
@@ -624,6 +635,8 @@ TG_DEV void tg_merge_stats_body(const TgMergeArgs& a, const TgPeerLink* link = n
     }
 }
 
+// tg_merge_stats, _b, _x: one thread per cell (_x: under the polling cap, see tg_capped_grid)
+TG_HD TgShape tg_merge_stats_shape(int C, int max_wg = 0) { return tg_shape(tg_capped_grid((C + 255) / 256, max_wg), 1, 256, 0); }
 TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_merge_stats(TgMergeArgs a) { tg_merge_stats_body<false>(a); }
 TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_merge_stats_b(const TgMergeArgs* argv) { tg_merge_stats_body<false>(argv[blockIdx.z]); }
 TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_merge_stats_x(TgMergeArgs a, TgPeerLink link) { tg_merge_stats_body<true>(a, &link); }

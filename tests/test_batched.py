@@ -169,6 +169,40 @@ def test_batched_folds_emulated(sim):
                   tol_loss=1e-5, tol_P=2e-5)
 
 
+def check_batched_seeds(device, precision, C, K, V, seeds, epochs):
+    """ONE problem from several seeds in one tg_batch against the same mappings trained alone: every history key and the logits
+    (M of tg_mapper_state), bit for bit."""
+    import tangram_amd as tg
+    import tangram_amd.mapping_optimizer as mo
+    from oracle import tangram_oracle as orc
+    data = orc.make_synthetic(C, K, V, seed=13)
+    kw = dict(S=data["S"], G=data["G"], d=data["d"], lambda_d=1, lambda_g1=1, lambda_g2=0.5)
+
+    def builder(seed):
+        return lambda: mo.Mapper(device=device, random_state=seed, gemm_precision=precision, **kw)
+
+    with batches_taken() as taken:
+        res, mappers = tg.train_many([builder(s) for s in seeds], epochs, 0.1, device=device, batched=True)
+    assert taken == [len(seeds)], taken
+    for i, s in enumerate(seeds):
+        alone = builder(s)()
+        P, hist = alone.train(num_epochs=epochs, learning_rate=0.1, print_each=None)
+        assert set(res[i][1]) == set(hist)
+        for k in hist:
+            np.testing.assert_array_equal(np.array(res[i][1][k], dtype=np.float64), np.array(hist[k], dtype=np.float64), err_msg=f"seed {s}: {k}")
+        Mb, Ma = mappers[i]._engine.logits()[0], alone._engine.logits()[0]
+        np.testing.assert_array_equal(Mb.cpu().numpy()[:, :V], Ma.cpu().numpy()[:, :V], err_msg=f"seed {s}: logits")
+        np.testing.assert_array_equal(res[i][0], P, err_msg=f"seed {s}: mapping")
+        assert np.isfinite(np.array(hist["total_loss"], dtype=np.float64)).all()
+
+
+def test_batched_emitter_column_blocks_emulated(sim):
+    """The solo and the batched emitter differ in shape on purpose (tg_dghat_emit_shape, tg_stats.h): 200 genes pad to 256 columns
+    and 100 spots are 7 blocks, so a mapping alone launches 2 column blocks per block of spots and the batch 1 -- same bits.
+    (GEMM path: 40 cells are past the clusters-mode bound.)"""
+    check_batched_seeds("cpu", "fp32", C=40, K=200, V=100, seeds=(1, 2, 3), epochs=4)
+
+
 def test_batched_folds_in_groups_emulated(sim):
     """From 8 mappings on tg_batch steps 2 - 4 groups of mappings (on streams of their own on the GPU): the per-group argument
     offsets, 9 Mapper folds as 4 + 5 and 13 MapperConstrained folds as 4 + 4 + 5."""
