@@ -279,6 +279,39 @@ int tg_sparse_map_build(const int64_t* indptr_dev, const int32_t* indices_dev, c
 int tg_sparse_map_project(const void* workspace_dev, int64_t n_cells, int64_t n_spots, int64_t nnz, const float* S_dev,
                           int64_t ld_s, int32_t n_genes, float* out_dev, int64_t ld_out, void* hip_stream);
 
+/* ---- agreement of repeated mappings ------------------------------------------------------------------------------------------
+ * What a tuning trial reports about R mappings of one problem trained from different seeds (mapping_parameter_tuning.py:42-82,
+ * :133-139), computed in ONE pass over R planes of one shape [n_rows][n_cols] -- no plane is written, copied or stacked:
+ *   pearson_out_dev            double [R (R - 1) / 2]: the Pearson correlation of every pair of planes (each flattened), in the order
+ *                              of np.tril_indices(R, -1): (1,0), (2,0), (2,1), (3,0) ...  Moments, products and sums are fp64.  A
+ *                              plane of zero variance gives 0 / 0 (the reference: NaN with a warning).
+ *   votes_out_dev              int32 [R][n_rows]: per plane and row the column of the largest element, ties to the lower column
+ *                              (np.argmax), decided on the element values; handles: the GLOBAL spot index (cfg.spot_offset + column).
+ *   vote_entropy_out_dev       float [n_rows]: -sum_s (n_s / R) log(n_s / R) / log(n_cols) over the distinct voted columns.
+ *   consensus_entropy_out_dev  float [n_rows]: entropy of the mean of the R rows / log(n_cols) (fp32 terms, fp64 sum).
+ * Each output may be NULL (not computed), not all of them.  1 <= R <= 8; at R = 1 there are no pairs and pearson_out_dev is not
+ * touched.  n_cols >= 2, because the entropies are divided by log(n_cols) and log(1) = 0.  workspace_dev: 8-byte aligned,
+ * tg_consistency_query_bytes(R, n_rows) bytes.  The calls are asynchronous, allocate nothing, write only the given outputs and
+ * the workspace, use fixed summation orders and no float atomics: the same inputs give the same bits on every call.
+ * TG_ERR_INVALID, never a fault: a NULL handle, plane or workspace, R out of range, n_cols < 2, ld < n_cols, n_rows < 1, sizes
+ * beyond the 32-bit indices of the kernels.                                                                                     */
+int tg_consistency_query_bytes(int32_t n_runs, int64_t n_rows, size_t* bytes_out);
+
+/* The planes are the mappings softmax(M) of R handles -- the very bits tg_mapper_result writes, computed from the logits; Mapper
+ * or MapperConstrained (softmax(M) without the filter, like adata_map.X), at any steps.  Enqueued on the handles' stream; their
+ * state and workspace are only read.  TG_ERR_INVALID also for handles that differ in n_cells, n_spots or pitch or were not created
+ * on one stream (the tg_batch rule); TG_ERR_UNSUPPORTED for a spot shard (n_ranks >= 1).                                        */
+int tg_mapper_consistency(tg_mapper* const* mappers, int32_t n_runs, void* workspace_dev, double* pearson_out_dev,
+                          float* vote_entropy_out_dev, float* consensus_entropy_out_dev, int32_t* votes_out_dev);
+
+/* The planes are R float matrices on the device (planes_dev: HOST array of R device pointers), n_rows x n_cols with the common
+ * row pitch ld >= n_cols (in floats), of any alignment; only the n_cols columns of a row are read.  Equal values give the bits
+ * of tg_mapper_consistency, whatever pitch and alignment (16-byte loads are used where every row start allows them).  Values
+ * order like floats with -0 == +0; a NaN makes the results undefined.  Enqueued on `hip_stream`.                                */
+int tg_planes_consistency(const float* const* planes_dev, int32_t n_runs, int64_t n_rows, int64_t n_cols, int64_t ld,
+                          void* workspace_dev, double* pearson_out_dev, float* vote_entropy_out_dev,
+                          float* consensus_entropy_out_dev, int32_t* votes_out_dev, void* hip_stream);
+
 /* ---- batched independent mappings ------------------------------------------------------------------------------
  * The reference trains independent mappings one after the other: one per held-out gene in `cross_val` (utils.py:576-600; 249 in
  * the tutorial), three seeds per trial in the tuner (mapping_parameter_tuning.py:109-131).  A tg_batch advances B Mapper handles

@@ -8,5 +8,8 @@ from .utils import project_genes                                  # noqa: F401
 from .sparse_project import project_sparse, SparseMap             # noqa: F401
 from .batched import train_many, MapperBatch                                   # noqa: F401
 from .cross_validation import cross_val, cv_data_gen                        # noqa: F401
+from . import mapping_parameter_tuning                                      # noqa: F401
+from .mapping_parameter_tuning import (pearson_corr, vote_entropy, consensus_entropy, mapping_consistency,   # noqa: F401
+                                       train_multiple_Mapper)
 
 __version__ = "0.1.0"

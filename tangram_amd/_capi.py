@@ -19,6 +19,7 @@ PRECISIONS = {"fp32": 0, "bf16": 1, "bf16x3": 2}
 H_NTERMS = 16
 TOPK_MAX = 64          # TG_TOPK_MAX / TG_TOPK_CHUNK of csrc/tg_topk.h (checked against tg_debug_topk_limits by the tests)
 TOPK_CHUNK = 8192
+CONSIST_MAX_RUNS = 8   # TG_CONSIST_MAX_RUNS of csrc/tg_consist.h
 H_TOTAL, H_MAIN, H_VG, H_KL, H_ENTROPY, H_L1, H_L2, H_NB, H_CT, H_COUNT, H_FREG, H_GETIS, H_MORAN, H_GEARY = range(14)
 
 
@@ -94,6 +95,12 @@ def _declare(lib):
     lib.tg_debug_sparse_map_layout.argtypes = [ct.c_int64, ct.c_int64, ct.POINTER(ct.c_int64)]
     for name in ("tg_sparse_map_query_bytes", "tg_sparse_map_build", "tg_sparse_map_project", "tg_debug_sparse_map_layout"):
         getattr(lib, name).restype = i32
+    lib.tg_consistency_query_bytes.argtypes = [ct.c_int32, ct.c_int64, ct.POINTER(ct.c_size_t)]
+    lib.tg_mapper_consistency.argtypes = [ct.POINTER(vp), ct.c_int32, vp, vp, vp, vp, vp]
+    lib.tg_planes_consistency.argtypes = [ct.POINTER(vp), ct.c_int32, ct.c_int64, ct.c_int64, ct.c_int64, vp, vp, vp, vp, vp, vp]
+    lib.tg_debug_planes_consistency.argtypes = lib.tg_planes_consistency.argtypes + [ct.c_int32]
+    for name in ("tg_consistency_query_bytes", "tg_mapper_consistency", "tg_planes_consistency", "tg_debug_planes_consistency"):
+        getattr(lib, name).restype = i32
     lib.tg_batch_query_bytes.argtypes = [i32]
     lib.tg_batch_query_bytes.restype = ct.c_size_t
     lib.tg_batch_create.argtypes = [ct.POINTER(vp), i32, vp, ct.POINTER(vp)]
@@ -131,7 +138,7 @@ EXPORTS = ["tg_abi_version", "tg_last_error", "tg_query_sizes", "tg_mapper_creat
            "tg_comm_all_reduce_sum", "tg_comm_all_gather", "tg_comm_destroy",
            "tg_mapper_attach_comm", "tg_mapper_result", "tg_mapper_result_topk", "tg_topk_merge",
            "tg_mapper_project", "tg_mapper_project_genes", "tg_csr_columns_to_dense", "tg_sparse_map_query_bytes", "tg_sparse_map_build",
-           "tg_sparse_map_project", "tg_csr_gather_columns", "tg_row_sums",
+           "tg_sparse_map_project", "tg_consistency_query_bytes", "tg_mapper_consistency", "tg_planes_consistency", "tg_csr_gather_columns", "tg_row_sums",
            "tg_cluster_aggregate", "tg_batch_query_bytes", "tg_batch_create", "tg_batch_step", "tg_batch_destroy", "tg_mapper_state", "tg_mapper_set_step",
            "tg_mapper_filter_state", "tg_mapper_profile",
            "tg_mapper_profile_read", "tg_mapper_validate", "tg_init_logits_normal", "tg_mapper_effective_precision"]

@@ -2165,6 +2165,140 @@ extern "C" int tg_sparse_map_project(const void* workspace_dev, int64_t n_cells,
     return TG_OK;
 }
 
+// ---- agreement of repeated mappings (tg_consist.h): the caller's workspace, nothing else written but the outputs
+template <class F>
+TG_SELECT void tg_with_runs(int n_runs, F&& f) {
+    switch (n_runs) {
+        case 1: f(tg_int<1>{}); break;
+        case 2: f(tg_int<2>{}); break;
+        case 3: f(tg_int<3>{}); break;
+        case 4: f(tg_int<4>{}); break;
+        case 5: f(tg_int<5>{}); break;
+        case 6: f(tg_int<6>{}); break;
+        case 7: f(tg_int<7>{}); break;
+        default: f(tg_int<8>{}); break;
+    }
+}
+
+static int tg_consist_shape(const char* who, int32_t n_runs, int64_t n_rows, int64_t n_cols, int64_t ld) {
+    if (n_runs < 1 || n_runs > TG_CONSIST_MAX_RUNS) return tg_fail(TG_ERR_INVALID, "%s: %d runs are outside [1, %d]", who, n_runs, TG_CONSIST_MAX_RUNS);
+    if (n_rows < 1 || n_cols < 2)
+        return tg_fail(TG_ERR_INVALID, "%s: %lld rows x %lld columns: at least one row and two columns (the entropies are divided by log(columns))", who,
+                       (long long)n_rows, (long long)n_cols);
+    if (ld < n_cols) return tg_fail(TG_ERR_INVALID, "%s: the row pitch %lld is smaller than the %lld columns", who, (long long)ld, (long long)n_cols);
+    // rows index int32 outputs and the row loop, columns are int32 with a chunk of headroom
+    if (n_rows > 0x7fffffffLL || n_cols > 0x7fffffffLL - 2 * TG_CONSIST_CHUNK)
+        return tg_fail(TG_ERR_INVALID, "%s: %lld rows or %lld columns exceed the 32-bit indices of the kernels", who, (long long)n_rows, (long long)n_cols);
+    return TG_OK;
+}
+
+extern "C" int tg_consistency_query_bytes(int32_t n_runs, int64_t n_rows, size_t* bytes_out) {
+    if (!bytes_out) return tg_fail(TG_ERR_INVALID, "consistency: bytes_out is NULL");
+    if (n_runs < 1 || n_runs > TG_CONSIST_MAX_RUNS) return tg_fail(TG_ERR_INVALID, "consistency: %d runs are outside [1, %d]", n_runs, TG_CONSIST_MAX_RUNS);
+    if (n_rows < 1 || n_rows > 0x7fffffffLL) return tg_fail(TG_ERR_INVALID, "consistency: %lld rows are outside [1, 2^31 - 1]", (long long)n_rows);
+    *bytes_out = tg_consist_bytes(n_runs, n_rows);
+    return TG_OK;
+}
+
+// both entry points end here, validated: a.plane (+ rshift / rinvz), ld, n_rows, n_cols, spot_offset are set
+static int tg_consist_launch(TgConsistArgs a, int mode, int n_runs, void* workspace_dev, double* pearson, float* vote_ent, float* cons_ent, int32_t* votes,
+                             tg_stream_t s, long long max_parts = TG_CONSIST_MAX_PARTS) {
+    const long long n_parts = tg_consist_parts(a.n_rows, max_parts);
+    a.inv_log_cols = (float)(1.0 / log((double)a.n_cols));
+    a.shift = 1.0 / (double)a.n_cols;
+    a.mom = pearson && n_runs > 1 ? (double*)workspace_dev : nullptr;    // the moments serve the correlations only
+    a.vote_ent = vote_ent; a.cons_ent = cons_ent; a.votes = (int*)votes;
+    tg_with_runs(n_runs, [&](auto rr) {
+        constexpr int R = decltype(rr)::value;
+        const TgShape shape = tg_consist_rows_shape(n_parts, R);
+        if (mode == TG_CONSIST_LOGITS) TG_LAUNCH((tg_consist_rows<R, TG_CONSIST_LOGITS>), shape, s, a);
+        else if (mode == TG_CONSIST_VEC) TG_LAUNCH((tg_consist_rows<R, TG_CONSIST_VEC>), shape, s, a);
+        else TG_LAUNCH((tg_consist_rows<R, TG_CONSIST_SCALAR>), shape, s, a);
+    });
+    if (a.mom)
+        TG_LAUNCH(tg_consist_finish, tg_shape(1, 1, 256, TG_CONSIST_FINISH_LDS), s, (const double*)a.mom, (int)n_parts, (int)n_runs,
+                  (double)a.n_rows * (double)a.n_cols, pearson);
+    TG_LAUNCH_CK();
+    return TG_OK;
+}
+
+extern "C" int tg_mapper_consistency(tg_mapper* const* mappers, int32_t n_runs, void* workspace_dev, double* pearson_out_dev,
+                                     float* vote_entropy_out_dev, float* consensus_entropy_out_dev, int32_t* votes_out_dev) {
+    if (!mappers) return tg_fail(TG_ERR_INVALID, "mapper consistency: the handle array is NULL");
+    if (n_runs < 1 || n_runs > TG_CONSIST_MAX_RUNS) return tg_fail(TG_ERR_INVALID, "mapper consistency: %d runs are outside [1, %d]", n_runs, TG_CONSIST_MAX_RUNS);
+    for (int i = 0; i < n_runs; ++i) {
+        if (!mappers[i]) return tg_fail(TG_ERR_INVALID, "mapper consistency: handle %d is NULL", i);
+        if (!mappers[i]->ready) return tg_fail(TG_ERR_STATE, "mapper consistency: handle %d is not ready", i);
+    }
+    const tg_mapper* m0 = mappers[0];
+    TgConsistArgs a;
+    memset(&a, 0, sizeof a);
+    for (int i = 0; i < n_runs; ++i) {
+        const tg_mapper* m = mappers[i];
+        if (m->cfg.n_ranks >= 1 || m->L.Vtot != m->L.V || m->comm)
+            return tg_fail(TG_ERR_UNSUPPORTED, "mapper consistency: handle %d is a spot shard (the sharded form is not available)", i);
+        if (m->L.C != m0->L.C || m->L.V != m0->L.V || m->L.Vp != m0->L.Vp || m->cfg.spot_offset != m0->cfg.spot_offset)
+            return tg_fail(TG_ERR_INVALID, "mapper consistency: handle %d is %d cells x %d spots (pitch %d), handle 0 %d x %d (pitch %d)", i, m->L.C, m->L.V,
+                           m->L.Vp, m0->L.C, m0->L.V, m0->L.Vp);
+        if (m->stream != m0->stream) return tg_fail(TG_ERR_INVALID, "mapper consistency: all handles must be created on the same stream");
+        a.plane[i] = (const float*)(m->st + m->L.s_M); a.rshift[i] = m->fp(m->L.o_rshift); a.rinvz[i] = m->fp(m->L.o_rinvz);
+    }
+    const int rc = tg_consist_shape("mapper consistency", n_runs, m0->L.C, m0->L.V, m0->L.Vp);
+    if (rc) return rc;
+    if (!workspace_dev) return tg_fail(TG_ERR_INVALID, "mapper consistency: the workspace is NULL");
+    if (!pearson_out_dev && !vote_entropy_out_dev && !consensus_entropy_out_dev && !votes_out_dev)
+        return tg_fail(TG_ERR_INVALID, "mapper consistency: every output is NULL");
+    a.ld = m0->L.Vp; a.n_rows = m0->L.C; a.n_cols = m0->L.V; a.spot_offset = m0->cfg.spot_offset;
+    return tg_consist_launch(a, TG_CONSIST_LOGITS, n_runs, workspace_dev, pearson_out_dev, vote_entropy_out_dev, consensus_entropy_out_dev, votes_out_dev,
+                             m0->stream);
+}
+
+static int tg_planes_consist(const float* const* planes_dev, int32_t n_runs, int64_t n_rows, int64_t n_cols, int64_t ld, void* workspace_dev,
+                             double* pearson_out_dev, float* vote_entropy_out_dev, float* consensus_entropy_out_dev, int32_t* votes_out_dev,
+                             void* hip_stream, long long max_parts) {
+    if (!planes_dev) return tg_fail(TG_ERR_INVALID, "planes consistency: the plane array is NULL");
+    const int rc = tg_consist_shape("planes consistency", n_runs, n_rows, n_cols, ld);
+    if (rc) return rc;
+    TgConsistArgs a;
+    memset(&a, 0, sizeof a);
+    bool vec = ld % 4 == 0;                                                // 16-byte loads: every row of every plane starts on a 16-byte boundary
+    for (int i = 0; i < n_runs; ++i) {
+        if (!planes_dev[i]) return tg_fail(TG_ERR_INVALID, "planes consistency: plane %d is NULL", i);
+        a.plane[i] = planes_dev[i];
+        vec = vec && ((uintptr_t)planes_dev[i] & 15) == 0;
+    }
+    if (!workspace_dev) return tg_fail(TG_ERR_INVALID, "planes consistency: the workspace is NULL");
+    if (!pearson_out_dev && !vote_entropy_out_dev && !consensus_entropy_out_dev && !votes_out_dev)
+        return tg_fail(TG_ERR_INVALID, "planes consistency: every output is NULL");
+    a.ld = ld; a.n_rows = (int)n_rows; a.n_cols = (int)n_cols; a.spot_offset = 0;
+    return tg_consist_launch(a, vec ? TG_CONSIST_VEC : TG_CONSIST_SCALAR, n_runs, workspace_dev, pearson_out_dev, vote_entropy_out_dev,
+                             consensus_entropy_out_dev, votes_out_dev, (tg_stream_t)hip_stream, max_parts);
+}
+
+extern "C" int tg_planes_consistency(const float* const* planes_dev, int32_t n_runs, int64_t n_rows, int64_t n_cols, int64_t ld, void* workspace_dev,
+                                     double* pearson_out_dev, float* vote_entropy_out_dev, float* consensus_entropy_out_dev, int32_t* votes_out_dev,
+                                     void* hip_stream) {
+    return tg_planes_consist(planes_dev, n_runs, n_rows, n_cols, ld, workspace_dev, pearson_out_dev, vote_entropy_out_dev, consensus_entropy_out_dev,
+                             votes_out_dev, hip_stream, TG_CONSIST_MAX_PARTS);
+}
+
+// tg_planes_consistency with at most max_parts (1 .. TG_CONSIST_MAX_PARTS) workgroups of tg_consist_rows: the tests walk the kernel's row loop
+// (a workgroup's second, third ... row) with a handful of rows instead of thousands.  The same checks, the same workspace size.
+extern "C" int tg_debug_planes_consistency(const float* const* planes_dev, int32_t n_runs, int64_t n_rows, int64_t n_cols, int64_t ld, void* workspace_dev,
+                                           double* pearson_out_dev, float* vote_entropy_out_dev, float* consensus_entropy_out_dev,
+                                           int32_t* votes_out_dev, void* hip_stream, int32_t max_parts) {
+    if (max_parts < 1 || max_parts > TG_CONSIST_MAX_PARTS)
+        return tg_fail(TG_ERR_INVALID, "planes consistency: %d workgroups are outside [1, %d]", max_parts, TG_CONSIST_MAX_PARTS);
+    return tg_planes_consist(planes_dev, n_runs, n_rows, n_cols, ld, workspace_dev, pearson_out_dev, vote_entropy_out_dev, consensus_entropy_out_dev,
+                             votes_out_dev, hip_stream, max_parts);
+}
+
+// the compile-time limits of tg_consist.h: out[0] = most runs, out[1] = columns per chunk, out[2] = most workgroups (partial moment sets)
+extern "C" int tg_debug_consist_limits(int32_t out[3]) {
+    out[0] = TG_CONSIST_MAX_RUNS; out[1] = TG_CONSIST_CHUNK; out[2] = TG_CONSIST_MAX_PARTS;
+    return TG_OK;
+}
+
 extern "C" int tg_csr_gather_columns(const int64_t* indptr_dev, const int32_t* indices_dev, const float* data_dev, int64_t n_rows,
                                      const int32_t* colmap_dev, int32_t n_out_cols, float* out_dev, int64_t ld_out, void* hip_stream) {
     if (!indptr_dev || !indices_dev || !data_dev || !colmap_dev || !out_dev) return tg_fail(TG_ERR_INVALID, "null argument");
