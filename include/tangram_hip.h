@@ -312,6 +312,24 @@ int tg_planes_consistency(const float* const* planes_dev, int32_t n_runs, int64_
                           void* workspace_dev, double* pearson_out_dev, float* vote_entropy_out_dev,
                           float* consensus_entropy_out_dev, int32_t* votes_out_dev, void* hip_stream);
 
+/* ---- per-gene scores of projected against measured expression ------------------------------------------------------------------
+ * What compare_spatial_geneexp reports per gene (utils.py:424-426: one dot product and one np.linalg.norm pair per gene over a
+ * spots x genes plane on the host), from two float planes on the device, pred_dev[n_spots][ld_pred] and meas_dev[n_spots][ld_meas];
+ * only the first n_genes columns of a row are read, the pitches (in floats, >= n_genes) and the alignment are free:
+ *   moments_out_dev   double [3][n_genes]: dot = sum_v pred meas, pp = sum_v pred^2, gg = sum_v meas^2
+ *   score_out_dev     double [n_genes]: dot / (sqrt(pp) sqrt(gg)), IEEE square roots and division; a zero norm gives 0 / 0 = NaN
+ *                     (the reference: NaN with a warning).
+ * Either output may be NULL (not written), not both.  Every element is converted to double, the products are formed in fp64 (exact
+ * for two fp32 factors) and added in fp64 in a FIXED order that depends on n_spots alone -- not on n_genes, the position of the
+ * column, the pitches, the alignment (16-byte loads are used where both planes allow them) or the call: a column gives the same
+ * bits in any block of any call.  No float atomics.  workspace_dev: 8-byte aligned, tg_gene_scores_query_bytes(n_spots, n_genes)
+ * bytes (per-slab partial moments).  No handle: enqueued on `hip_stream`, asynchronous, allocates nothing, writes only the given
+ * outputs and the workspace.  TG_ERR_INVALID, never a fault: a NULL plane, workspace or bytes_out, both outputs NULL, n_spots < 1,
+ * n_genes < 1, a pitch below n_genes, sizes beyond the 32-bit indices and grids of the kernels.                                  */
+int tg_gene_scores_query_bytes(int64_t n_spots, int32_t n_genes, size_t* bytes_out);
+int tg_gene_scores(const float* pred_dev, int64_t ld_pred, const float* meas_dev, int64_t ld_meas, int64_t n_spots,
+                   int32_t n_genes, void* workspace_dev, double* moments_out_dev, double* score_out_dev, void* hip_stream);
+
 /* ---- batched independent mappings ------------------------------------------------------------------------------
  * The reference trains independent mappings one after the other: one per held-out gene in `cross_val` (utils.py:576-600; 249 in
  * the tutorial), three seeds per trial in the tuner (mapping_parameter_tuning.py:109-131).  A tg_batch advances B Mapper handles

@@ -101,6 +101,9 @@ def _declare(lib):
     lib.tg_debug_planes_consistency.argtypes = lib.tg_planes_consistency.argtypes + [ct.c_int32]
     for name in ("tg_consistency_query_bytes", "tg_mapper_consistency", "tg_planes_consistency", "tg_debug_planes_consistency"):
         getattr(lib, name).restype = i32
+    lib.tg_gene_scores_query_bytes.argtypes = [ct.c_int64, ct.c_int32, ct.POINTER(ct.c_size_t)]
+    lib.tg_gene_scores.argtypes = [vp, ct.c_int64, vp, ct.c_int64, ct.c_int64, ct.c_int32, vp, vp, vp, vp]
+    lib.tg_gene_scores_query_bytes.restype = lib.tg_gene_scores.restype = i32
     lib.tg_batch_query_bytes.argtypes = [i32]
     lib.tg_batch_query_bytes.restype = ct.c_size_t
     lib.tg_batch_create.argtypes = [ct.POINTER(vp), i32, vp, ct.POINTER(vp)]
@@ -138,7 +141,7 @@ EXPORTS = ["tg_abi_version", "tg_last_error", "tg_query_sizes", "tg_mapper_creat
            "tg_comm_all_reduce_sum", "tg_comm_all_gather", "tg_comm_destroy",
            "tg_mapper_attach_comm", "tg_mapper_result", "tg_mapper_result_topk", "tg_topk_merge",
            "tg_mapper_project", "tg_mapper_project_genes", "tg_csr_columns_to_dense", "tg_sparse_map_query_bytes", "tg_sparse_map_build",
-           "tg_sparse_map_project", "tg_consistency_query_bytes", "tg_mapper_consistency", "tg_planes_consistency", "tg_csr_gather_columns", "tg_row_sums",
+           "tg_sparse_map_project", "tg_consistency_query_bytes", "tg_mapper_consistency", "tg_planes_consistency", "tg_gene_scores_query_bytes", "tg_gene_scores", "tg_csr_gather_columns", "tg_row_sums",
            "tg_cluster_aggregate", "tg_batch_query_bytes", "tg_batch_create", "tg_batch_step", "tg_batch_destroy", "tg_mapper_state", "tg_mapper_set_step",
            "tg_mapper_filter_state", "tg_mapper_profile",
            "tg_mapper_profile_read", "tg_mapper_validate", "tg_init_logits_normal", "tg_mapper_effective_precision"]

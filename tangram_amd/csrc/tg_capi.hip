@@ -2,6 +2,7 @@
 // Enqueues the kernels of tg_kernels.h on the caller's stream; allocates nothing on the device.
 #include "../../include/tangram_hip.h"
 #include "tg_kernels.h"
+#include "tg_score.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -2296,6 +2297,58 @@ extern "C" int tg_debug_planes_consistency(const float* const* planes_dev, int32
 // the compile-time limits of tg_consist.h: out[0] = most runs, out[1] = columns per chunk, out[2] = most workgroups (partial moment sets)
 extern "C" int tg_debug_consist_limits(int32_t out[3]) {
     out[0] = TG_CONSIST_MAX_RUNS; out[1] = TG_CONSIST_CHUNK; out[2] = TG_CONSIST_MAX_PARTS;
+    return TG_OK;
+}
+
+// ---- per-gene cosine scores of two spots x genes planes (tg_score.h): no handle, the caller's workspace, the caller's stream
+static int tg_score_sizes(const char* who, int64_t n_spots, int64_t n_genes, long long* n_strips, long long* n_slabs) {
+    if (n_spots < 1 || n_genes < 1) return tg_fail(TG_ERR_INVALID, "%s: %lld spots x %lld genes: at least one of each", who, (long long)n_spots, (long long)n_genes);
+    // rows and columns are int32 with a slab / a strip of headroom, the grid of tg_score_partials is strips x slabs in blockIdx.x
+    if (n_spots > 0x7fffffffLL - TG_SCORE_SLAB || n_genes > 0x7fffffffLL - TG_SCORE_STRIP ||
+        tg_score_strips(n_genes) * tg_score_slabs(n_spots) > 0x7fffffffLL)
+        return tg_fail(TG_ERR_INVALID, "%s: %lld spots x %lld genes exceed the 32-bit indices and grids of the kernels", who, (long long)n_spots, (long long)n_genes);
+    *n_strips = tg_score_strips(n_genes); *n_slabs = tg_score_slabs(n_spots);
+    return TG_OK;
+}
+
+extern "C" int tg_gene_scores_query_bytes(int64_t n_spots, int32_t n_genes, size_t* bytes_out) {
+    if (!bytes_out) return tg_fail(TG_ERR_INVALID, "gene scores: bytes_out is NULL");
+    long long n_strips, n_slabs;
+    const int rc = tg_score_sizes("gene scores", n_spots, n_genes, &n_strips, &n_slabs);
+    if (rc) return rc;
+    *bytes_out = tg_score_bytes(n_spots, n_genes);
+    return TG_OK;
+}
+
+extern "C" int tg_gene_scores(const float* pred_dev, int64_t ld_pred, const float* meas_dev, int64_t ld_meas, int64_t n_spots, int32_t n_genes,
+                              void* workspace_dev, double* moments_out_dev, double* score_out_dev, void* hip_stream) {
+    long long n_strips, n_slabs;
+    const int rc = tg_score_sizes("gene scores", n_spots, n_genes, &n_strips, &n_slabs);
+    if (rc) return rc;
+    if (!pred_dev || !meas_dev) return tg_fail(TG_ERR_INVALID, "gene scores: the %s plane is NULL", pred_dev ? "measured" : "predicted");
+    if (ld_pred < n_genes || ld_meas < n_genes)
+        return tg_fail(TG_ERR_INVALID, "gene scores: the row pitches %lld (predicted) and %lld (measured) must be at least the %d genes", (long long)ld_pred,
+                       (long long)ld_meas, n_genes);
+    if (!workspace_dev || ((uintptr_t)workspace_dev & 7)) return tg_fail(TG_ERR_INVALID, "gene scores: the workspace is NULL or not 8-byte aligned");
+    if (!moments_out_dev && !score_out_dev) return tg_fail(TG_ERR_INVALID, "gene scores: every output is NULL");
+    TgScoreArgs a;
+    a.pred = pred_dev; a.meas = meas_dev; a.ld_pred = ld_pred; a.ld_meas = ld_meas;
+    a.n_spots = (int)n_spots; a.n_genes = n_genes; a.n_strips = (int)n_strips; a.part = (double*)workspace_dev;
+    // 16-byte loads where every row of both planes starts on a 16-byte boundary (strip offsets are multiples of 1 KB)
+    const bool vec = (((uintptr_t)pred_dev | (uintptr_t)meas_dev) & 15) == 0 && ld_pred % TG_SCORE_VEC == 0 && ld_meas % TG_SCORE_VEC == 0;
+    tg_stream_t s = (tg_stream_t)hip_stream;
+    const TgShape shape = tg_score_partials_shape(n_strips, n_slabs);
+    if (vec) TG_LAUNCH((tg_score_partials<true>), shape, s, a);
+    else TG_LAUNCH((tg_score_partials<false>), shape, s, a);
+    TG_LAUNCH(tg_score_finish, tg_score_finish_shape(n_genes), s, (const double*)a.part, (int)n_slabs, (int)n_genes, moments_out_dev, score_out_dev);
+    TG_LAUNCH_CK();
+    return TG_OK;
+}
+
+// the compile-time constants of tg_score.h: strip width in genes, floats of the 16-byte path, slab height, rows per wave, and of
+// tg_score_finish: threads per gene (= slabs per round), genes per workgroup
+extern "C" int tg_debug_score_limits(int32_t out[6]) {
+    out[0] = TG_SCORE_STRIP; out[1] = TG_SCORE_VEC; out[2] = TG_SCORE_SLAB; out[3] = TG_SCORE_RPW; out[4] = TG_SCORE_FIN_TPG; out[5] = TG_SCORE_FIN_GENES;
     return TG_OK;
 }
 

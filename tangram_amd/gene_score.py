@@ -1,0 +1,117 @@
+"""Per-gene cosine scores of a predicted against a measured spots x genes plane on the device (csrc/tg_score.h, tg_gene_scores):
+what `compare_spatial_geneexp` computes with one `np.linalg.norm` pair per gene on the host (reference tangram/utils.py:424-426).
+
+  gene_scores     score[j] = <pred[:, j], meas[:, j]> / (|pred[:, j]| |meas[:, j]|) for two planes of equal shape, float64; optionally the
+                  three moments (dot, |pred|^2, |meas|^2) they are made of
+  GeneScorer      the workspace and outputs of planes of one height, reused block of genes by block of genes
+  GeneBlocks      selected gene columns of an AnnData matrix (dense or scipy-sparse) as dense float32 device blocks
+
+Every element is converted to double, products and sums are fp64 in an order that depends on the number of spots alone: a column
+gives the same bits in any block of any call.  Everything goes through the C ABI; torch only owns the memory.
+"""
+from __future__ import annotations
+
+import ctypes as ct
+
+import numpy as np
+import torch
+
+from . import _capi
+from .preprocess import DeviceCSR, _call, _check_device, _stream
+
+
+def _plane(x, device, name):
+    x = torch.as_tensor(x) if not isinstance(x, torch.Tensor) else x
+    if x.dim() != 2:
+        raise ValueError(f"{name} must be a [n_spots, n_genes] matrix")
+    x = x.to(device=device, dtype=torch.float32)
+    if x.shape[1] > 1 and x.stride(1) != 1:
+        x = x.contiguous()
+    return x
+
+
+def _pitch(x):
+    return int(x.stride(0)) if x.shape[0] > 1 else max(int(x.stride(0)), int(x.shape[1]))
+
+
+class GeneScorer:
+    """Scores planes of `n_spots` rows and at most `max_genes` columns on `device`; nothing is allocated per call."""
+
+    def __init__(self, n_spots, max_genes, device):
+        self.device = _check_device(device)
+        self.n_spots, self.max_genes = int(n_spots), int(max_genes)
+        nbytes = ct.c_size_t()
+        _capi.check(_capi.lib().tg_gene_scores_query_bytes(self.n_spots, self.max_genes, ct.byref(nbytes)))
+        self.workspace = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+
+    def score_into(self, pred, meas, score=None, moments=None):
+        """pred, meas: float32 [n_spots, n] device tensors with unit column stride (views with a pitch are taken as they are);
+        score: float64 [n] or None, moments: contiguous float64 [3, n] or None (not both None), written in place."""
+        n = int(pred.shape[1])
+        if pred.shape != meas.shape:
+            raise ValueError(f"the predicted plane is {tuple(pred.shape)}, the measured one {tuple(meas.shape)}")
+        if int(pred.shape[0]) != self.n_spots or n > self.max_genes:
+            raise ValueError(f"this scorer takes planes of {self.n_spots} spots x at most {self.max_genes} genes")
+        for t, name in ((pred, "pred"), (meas, "meas")):
+            if t.dtype != torch.float32 or t.device != self.device or (n > 1 and t.stride(1) != 1):
+                raise ValueError(f"{name} must be a float32 tensor on {self.device} with unit column stride")
+        for t, shape, name in ((score, (n,), "score"), (moments, (3, n), "moments")):
+            if t is not None and (t.dtype != torch.float64 or t.device != self.device or tuple(t.shape) != shape or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous float64 tensor of shape {shape} on {self.device}")
+        _call(self.device, _capi.lib().tg_gene_scores, pred.data_ptr() or None, _pitch(pred), meas.data_ptr() or None, _pitch(meas),
+              self.n_spots, n, self.workspace.data_ptr(), moments.data_ptr() if moments is not None else None,
+              score.data_ptr() if score is not None else None, _stream(self.device))
+
+
+def gene_scores(pred, meas, *, moments=False, device=None):
+    """Cosine score of every gene column of `pred` against the same column of `meas` -> float64 tensor [n_genes] on the device;
+    `moments=True`: (scores, moments [3, n_genes] = dot, sum pred^2, sum meas^2).  pred, meas: device tensors or host arrays of equal
+    shape [n_spots, n_genes] (taken as float32; views with a row pitch are read in place).  A gene whose predicted or measured column
+    is all zero scores NaN, as in the reference.  `device`: default the device of a tensor argument, else cuda:0."""
+    if device is None:
+        device = next((t.device for t in (pred, meas) if isinstance(t, torch.Tensor) and t.device.type == "cuda"), None)
+        if device is None:
+            device = next((t.device for t in (pred, meas) if isinstance(t, torch.Tensor)), torch.device("cuda:0"))
+    device = _check_device(device)
+    if tuple(pred.shape) != tuple(meas.shape):
+        raise ValueError(f"pred is {tuple(pred.shape)}, meas is {tuple(meas.shape)}: the two planes must have the same shape")
+    pred, meas = _plane(pred, device, "pred"), _plane(meas, device, "meas")
+    n_spots, n = (int(s) for s in pred.shape)
+    scorer = GeneScorer(n_spots, n, device)
+    score = torch.empty(n, dtype=torch.float64, device=device)
+    mom = torch.empty((3, n), dtype=torch.float64, device=device) if moments else None
+    scorer.score_into(pred, meas, score, mom)
+    return (score, mom) if moments else score
+
+
+class GeneBlocks:
+    """The gene columns `idx` (in that order) of the matrix X [n_obs, n_vars] -- dense, or scipy-sparse: then the selection is uploaded
+    once as CSR and every block is expanded on the device (tg_csr_columns_to_dense).  `fill(k0, kc, out)` writes the columns
+    k0 .. k0 + kc of the selection into the float32 device tensor `out[:, :kc]`."""
+
+    def __init__(self, X, idx, device):
+        self.device = _check_device(device)
+        self.idx = np.asarray(idx, dtype=np.int64)
+        self.n_obs = int(X.shape[0])
+        self.csr = self.dense = None
+        if hasattr(X, "tocsr") and not isinstance(X, torch.Tensor):
+            sel = X.tocsr()[:, self.idx]
+            self.csr = DeviceCSR(sel, self.device) if sel.nnz else "empty"     # (an all-zero selection: no NULL arrays for the library)
+        else:
+            self.dense = X
+
+    def fill(self, k0, kc, out):
+        view = out[:, :kc]
+        if self.dense is not None:
+            cols = self.idx[k0:k0 + kc]
+            if isinstance(self.dense, torch.Tensor):
+                view.copy_(self.dense[:, torch.as_tensor(cols, device=self.dense.device)])
+            else:
+                view.copy_(torch.as_tensor(np.ascontiguousarray(np.asarray(self.dense)[:, cols], dtype=np.float32)))
+        elif self.csr == "empty":
+            view.zero_()
+        else:
+            c = self.csr
+            _call(self.device, _capi.lib().tg_csr_columns_to_dense, c.indptr.data_ptr(), c.indices.data_ptr(), c.data.data_ptr(), self.n_obs,
+                  int(k0), int(kc), out.data_ptr(), _pitch(out), _stream(self.device))
+        return view

@@ -59,6 +59,26 @@ def _projection_engine(adata_map, device, gemm_precision):
     return HipMapperEngine(S1, G1, M0, device=device, precision=gemm_precision, lambdas=dict(lambda_g1=1.0)), rows
 
 
+def _prepare_sc(adata_map, adata_sc, cluster_label, scale):
+    """What project_genes does to `adata_sc` before the product (reference utils.py:351-365) -> (the prepared adata_sc, its matrix:
+    scipy-sparse as it is, or dense float32)."""
+    adata_sc.var.index = [g.lower() for g in adata_sc.var.index]                     # :351
+    adata_sc.var.index = _make_unique(list(adata_sc.var.index))                      # :354
+    X = adata_sc.X
+    n_cells = np.asarray((X != 0).sum(axis=0)).reshape(-1)                           # :357 filter_genes(min_cells=1)
+    keep = n_cells >= 1
+    if not keep.all():
+        adata_sc = adata_sc[:, list(adata_sc.var.index[keep])]
+    adata_sc.var["n_cells"] = n_cells[keep]
+    if cluster_label:                                                                # :359-360
+        adata_sc = mu.adata_to_cluster_expression(adata_sc, cluster_label, scale=scale)
+    if not adata_map.obs.index.equals(adata_sc.obs.index):                           # :362-363
+        raise ValueError("The two AnnDatas need to have same `obs` index.")
+    X_sc = adata_sc.X                                                                # :364-365: sparse stays sparse, the gene blocks
+    S_all = X_sc if hasattr(X_sc, "tocsr") else np.ascontiguousarray(mu._dense(X_sc), dtype=np.float32)   # are expanded on the device
+    return adata_sc, S_all
+
+
 def project_genes(adata_map, adata_sc, cluster_label=None, scale=True, *, mapper=None, device="cuda:0",
                   gemm_precision="bf16x3", truncated=False):
     """Transfer gene expression from the single cell data onto space (reference utils.py:338-375).
@@ -77,20 +97,7 @@ def project_genes(adata_map, adata_sc, cluster_label=None, scale=True, *, mapper
     expression.  ValueError with a dense `adata_map.X` or together with `mapper=`.
     Unlike the reference (`sc.pp.filter_genes`, `var_names_make_unique` mutate the caller's AnnData in place, :351-357),
     only `adata_sc.var.index` is rewritten in place; the gene filter and `n_cells` land on a view."""
-    adata_sc.var.index = [g.lower() for g in adata_sc.var.index]                     # :351
-    adata_sc.var.index = _make_unique(list(adata_sc.var.index))                      # :354
-    X = adata_sc.X
-    n_cells = np.asarray((X != 0).sum(axis=0)).reshape(-1)                           # :357 filter_genes(min_cells=1)
-    keep = n_cells >= 1
-    if not keep.all():
-        adata_sc = adata_sc[:, list(adata_sc.var.index[keep])]
-    adata_sc.var["n_cells"] = n_cells[keep]
-    if cluster_label:                                                                # :359-360
-        adata_sc = mu.adata_to_cluster_expression(adata_sc, cluster_label, scale=scale)
-    if not adata_map.obs.index.equals(adata_sc.obs.index):                           # :362-363
-        raise ValueError("The two AnnDatas need to have same `obs` index.")
-    X_sc = adata_sc.X                                                                # :364-365: sparse stays sparse, the gene blocks
-    S_all = X_sc if hasattr(X_sc, "tocsr") else np.ascontiguousarray(mu._dense(X_sc), dtype=np.float32)   # are expanded on the device
+    adata_sc, S_all = _prepare_sc(adata_map, adata_sc, cluster_label, scale)
     own = mapper is None
     if truncated:
         if not own:
@@ -139,3 +146,171 @@ def project_genes(adata_map, adata_sc, cluster_label=None, scale=True, *, mapper
     training_genes = adata_map.uns["train_genes_df"].index.values                    # :370-371
     adata_ge.var["is_training"] = adata_ge.var.index.isin(training_genes)
     return adata_ge
+
+
+_MISSING_SP = "Missing tangram parameters. Run `pp_adatas()`."
+_MISSING_GE = "Missing tangram parameters. Use `project_genes()` to get adata_ge."
+_TANGRAM_KEYS = {"training_genes", "overlap_genes"}
+
+
+def _check_score_inputs(uns_ge, adata_sp, genes):
+    """The checks compare_spatial_geneexp runs before it computes anything (reference utils.py:394-408) -> the genes to score."""
+    if not _TANGRAM_KEYS.issubset(set(adata_sp.uns.keys())):
+        raise ValueError(_MISSING_SP)
+    if not _TANGRAM_KEYS.issubset(set(uns_ge.keys())):
+        raise ValueError(_MISSING_GE)
+    assert list(adata_sp.uns["overlap_genes"]) == list(uns_ge["overlap_genes"])
+    return list(uns_ge["overlap_genes"] if genes is None else genes)
+
+
+def _columns_of(var, genes, what):
+    idx = var.index.get_indexer(genes)
+    if (idx < 0).any():
+        raise KeyError(f"genes missing from {what}: {[g for g, i in zip(genes, idx) if i < 0][:5]}")
+    return idx
+
+
+def _score_frame(scores, overlap_genes, var_ge, adata_sp, adata_sc, genes):
+    """The DataFrame of compare_spatial_geneexp from the per-gene scores (reference utils.py:428-463)."""
+    df_g = pd.DataFrame(np.asarray(scores, dtype=np.float64), overlap_genes, columns=["score"])
+    for var in (var_ge, adata_sp.var):
+        if "is_training" in var.keys():
+            df_g["is_training"] = var["is_training"]
+    df_g["sparsity_sp"] = adata_sp.var.loc[overlap_genes, "sparsity"]
+    if adata_sc is not None:
+        if not _TANGRAM_KEYS.issubset(set(adata_sc.uns.keys())):
+            raise ValueError(_MISSING_SP)
+        assert list(adata_sc.uns["overlap_genes"]) == list(adata_sp.uns["overlap_genes"])
+        mu.annotate_gene_sparsity(adata_sc)
+        df_g = df_g.merge(pd.DataFrame(adata_sc.var.loc[overlap_genes, "sparsity"]), left_index=True, right_index=True)
+        df_g.rename({"sparsity": "sparsity_sc"}, inplace=True, axis="columns")
+        df_g["sparsity_diff"] = df_g["sparsity_sp"] - df_g["sparsity_sc"]
+    if genes is not None:
+        df_g = df_g.loc[genes]
+    return df_g.sort_values(by="score", ascending=False)
+
+
+def compare_spatial_geneexp(adata_ge, adata_sp, adata_sc=None, genes=None, *, device="cuda:0", gene_block=1024):
+    """Compares generated spatial data with the true spatial data (reference utils.py:377-463): a DataFrame indexed by gene with the
+    columns `score` (cosine similarity of the gene's projected and measured expression over the spots), `is_training` (when
+    `adata_ge.var` or `adata_sp.var` has it), `sparsity_sp`, and -- only when `adata_sc` is passed -- `sparsity_sc` and `sparsity_diff`
+    (= sparsity_sp - sparsity_sc); subset and ordered by `genes` when given, then sorted by descending score.  Same argument
+    meaning, ValueError conditions and assertions as the reference; like it, the call writes `var["sparsity"]` of adata_sp (and
+    adata_sc).  The scored columns of `adata_ge.X` and `adata_sp.X` (dense or scipy-sparse: uploaded once as CSR, expanded on the
+    device) go to `device` in blocks of `gene_block` genes and are reduced there (tg_gene_scores): products and sums in float64 of the
+    float32 values, where the reference takes NumPy norms in the matrices' own precision.  The root logger is left alone."""
+    from .gene_score import GeneBlocks, GeneScorer
+    overlap_genes = _check_score_inputs(adata_ge.uns, adata_sp, genes)
+    mu.annotate_gene_sparsity(adata_sp)
+    if adata_ge.X.shape[0] != adata_sp.X.shape[0]:
+        raise ValueError(f"adata_ge has {adata_ge.X.shape[0]} spots, adata_sp has {adata_sp.X.shape[0]}")
+    n_spots, n = int(adata_sp.X.shape[0]), len(overlap_genes)
+    dev = torch.device(device)
+    ge = GeneBlocks(adata_ge.X, _columns_of(adata_ge.var, overlap_genes, "adata_ge"), dev)
+    sp_ = GeneBlocks(adata_sp.X, _columns_of(adata_sp.var, overlap_genes, "adata_sp"), dev)
+    dev = ge.device
+    kb = max(1, min(int(gene_block), n))
+    scores = torch.empty(n, dtype=torch.float64, device=dev)
+    if n:
+        scorer = GeneScorer(n_spots, kb, dev)
+        pred, meas = (torch.empty((n_spots, kb), dtype=torch.float32, device=dev) for _ in range(2))
+        for k0 in range(0, n, kb):
+            kc = min(kb, n - k0)
+            scorer.score_into(ge.fill(k0, kc, pred), sp_.fill(k0, kc, meas), scores[k0:k0 + kc])
+    return _score_frame(scores.cpu().numpy(), overlap_genes, adata_ge.var, adata_sp, adata_sc, genes)
+
+
+def _block_projection(adata_map, n_cells, mapper, truncated, device, gemm_precision):
+    """One of project_genes' three routes as `project(S_block [n_cells, kc] float32 device tensor) -> [n_spots, kc] device tensor`,
+    with its device, its number of spots and what to call when done.  The ValueError rules are those of project_genes."""
+    own = mapper is None
+    nothing = lambda: None                                                            # noqa: E731
+    if truncated:
+        if not own:
+            raise ValueError("truncated=True projects the sparse adata_map.X itself: it cannot be combined with mapper=")
+        if not hasattr(adata_map.X, "tocsr"):
+            raise ValueError("truncated=True needs a sparse adata_map.X (the top_k= result); a dense mapping is projected without it")
+        from .sparse_project import SparseMap
+        sm = SparseMap(adata_map.X, device, n_cells=n_cells)
+        scratch = {}
+
+        def project(S_blk):
+            kc = int(S_blk.shape[1])
+            if "out" not in scratch or scratch["out"].shape[1] < kc:
+                scratch["out"] = torch.empty((sm.n_spots, kc), dtype=torch.float32, device=sm.device)
+            return sm.project_into(S_blk, scratch["out"][:, :kc])
+        return project, sm.device, sm.n_spots, nothing
+    if own and hasattr(adata_map.X, "tocsr"):
+        raise ValueError("adata_map.X is sparse (map_cells_to_space(..., top_k=k) keeps each cell's k most probable spots only): "
+                         "project with the trained mapping instead -- map with keep_mapper=True and pass "
+                         "mapper=adata_map._tangram_amd_mapper -- or project the truncated matrix itself with truncated=True")
+    if not own:
+        if getattr(mapper, "_sharded", None) is not None:
+            raise ValueError("score_genes does not take a spot-sharded mapper: every rank holds the moments of its own spots only, and "
+                             "their exchange is not available; project with project_genes and score with compare_spatial_geneexp")
+        engine = mapper._engine
+        if engine.C != n_cells:
+            raise ValueError("The two AnnDatas need to have same `obs` index.")
+        from .mapping_optimizer import MapperConstrained
+        if isinstance(mapper, MapperConstrained):                                     # softmax(M) without the filter, like adata_map.X
+            return (lambda S_blk: mapper.project_genes_device(S_blk, unfiltered=True)), engine.device, engine.V, nothing
+        return (lambda S_blk: mapper.project_genes_device(S_blk)), engine.device, engine.V, nothing
+    engine, rows = _projection_engine(adata_map, torch.device(device), gemm_precision)
+    if engine.C != n_cells:
+        engine.release()
+        raise ValueError("The two AnnDatas need to have same `obs` index.")
+    scale = None
+    if np.abs(rows - 1.0).max() > 1e-6:                                               # not row-stochastic: P^T S = (P / r)^T (r S)
+        scale = torch.as_tensor(rows, dtype=torch.float64, device=engine.device)[:, None]
+
+    def project(S_blk):
+        if scale is not None:
+            S_blk = (S_blk.double() * scale).float()
+        return engine.project_genes(S_blk, unfiltered=True)
+    return project, engine.device, engine.V, engine.release
+
+
+def score_genes(adata_map, adata_sc, adata_sp, cluster_label=None, scale=True, genes=None, *, mapper=None, truncated=False,
+                device="cuda:0", gemm_precision="bf16x3", gene_block=1024):
+    """`compare_spatial_geneexp(project_genes(adata_map, adata_sc, cluster_label, scale, ...), adata_sp, adata_sc, genes)` without the
+    projected plane: the same DataFrame (index, columns, `is_training`, sparsities, order), but no spots x genes array ever exists on
+    the host and none wider than `gene_block` genes on the device.  `adata_sc` is prepared as project_genes prepares it; only the
+    scored genes -- `adata_sc.uns["overlap_genes"]`, or `genes` -- are projected: block by block their columns of the single-cell
+    matrix are gathered on the device (a dense matrix is uploaded once; a scipy-sparse one as CSR), projected by the route the
+    keywords select exactly as in project_genes (`mapper=`: the mapping resident in HBM; a dense `adata_map.X`; `truncated=True`: the
+    sparse `adata_map.X` itself; the same ValueErrors), and scored against the same genes of `adata_sp.X` (tg_gene_scores), the
+    scratch reused.  A spot-sharded mapper is refused with a ValueError."""
+    from . import preprocess as pre
+    from .gene_score import GeneBlocks, GeneScorer
+    adata_sc_p, S_all = _prepare_sc(adata_map, adata_sc, cluster_label, scale)
+    n_cells = int(S_all.shape[0])
+    project, dev, n_spots, done = _block_projection(adata_map, n_cells, mapper, truncated, device, gemm_precision)
+    try:
+        overlap_genes = _check_score_inputs(adata_sc_p.uns, adata_sp, genes)
+        mu.annotate_gene_sparsity(adata_sp)
+        if n_spots != adata_sp.X.shape[0]:
+            raise ValueError(f"the mapping has {n_spots} spots, adata_sp has {adata_sp.X.shape[0]}")
+        var_ge = adata_sc_p.var.copy()
+        var_ge["is_training"] = var_ge.index.isin(adata_map.uns["train_genes_df"].index.values)
+        idx_sc = _columns_of(var_ge, overlap_genes, "adata_sc")
+        sp_ = GeneBlocks(adata_sp.X, _columns_of(adata_sp.var, overlap_genes, "adata_sp"), dev)
+        n = len(overlap_genes)
+        kb = max(1, min(int(gene_block), n))
+        scores = torch.empty(n, dtype=torch.float64, device=dev)
+        if n:
+            sparse_s = hasattr(S_all, "tocsr")
+            S_dev = pre.DeviceCSR(S_all, dev) if sparse_s else torch.as_tensor(S_all).to(device=dev, dtype=torch.float32)
+            scorer = GeneScorer(n_spots, kb, dev)
+            meas = torch.empty((n_spots, kb), dtype=torch.float32, device=dev)
+            for k0 in range(0, n, kb):
+                kc = min(kb, n - k0)
+                cols = idx_sc[k0:k0 + kc]
+                if sparse_s:
+                    S_blk = pre.gather_training_genes(S_dev, cols, dev)
+                else:
+                    S_blk = S_dev.index_select(1, torch.as_tensor(cols, dtype=torch.int64, device=dev))
+                scorer.score_into(project(S_blk), sp_.fill(k0, kc, meas), scores[k0:k0 + kc])
+        scores = scores.cpu().numpy()
+    finally:
+        done()
+    return _score_frame(scores, overlap_genes, var_ge, adata_sp, adata_sc, genes)
