@@ -56,95 +56,72 @@ _lib = None
 _is_sim = False
 
 
+def _signatures():
+    """Every entry point of include/tangram_hip.h that this package calls: name -> (restype, argtypes).  The one list of names."""
+    vp, i32, i64, f32, sz, P = ct.c_void_p, ct.c_int32, ct.c_int64, ct.c_float, ct.c_size_t, ct.POINTER
+    planes = [P(vp), i32, i64, i64, i64, vp, vp, vp, vp, vp, vp]
+    return {
+        "tg_abi_version": (i32, []),
+        "tg_last_error": (ct.c_char_p, []),
+        "tg_query_sizes": (i32, [P(TgConfig), P(TgSizes)]),
+        "tg_mapper_create": (i32, [P(TgConfig), P(TgInputs), vp, vp, vp, P(vp)]),
+        "tg_mapper_destroy": (None, [vp]),
+        "tg_mapper_step": (i32, [vp, i32, f32, vp, i32]),
+        "tg_comm_create_callbacks": (i32, [i32, i32, ALL_REDUCE_FN, ALL_GATHER_FN, vp, P(vp)]),
+        "tg_comm_rccl_unique_id": (i32, [ct.c_char_p, vp]),
+        "tg_comm_create_rccl": (i32, [ct.c_char_p, vp, i32, i32, P(vp)]),
+        "tg_comm_peer_create": (i32, [i32, i32, sz, i32, vp, P(vp)]),
+        "tg_comm_peer_create_stepped": (i32, [i32, i32, sz, sz, i32, i32, vp, P(vp)]),
+        "tg_comm_peer_connect": (i32, [vp, vp]),
+        "tg_comm_peer_status": (i32, [vp, P(i32)]),
+        "tg_comm_peer_set_timeout_ms": (i32, [vp, ct.c_double]),
+        "tg_comm_all_reduce_sum": (i32, [vp, vp, sz, vp]),
+        "tg_comm_all_gather": (i32, [vp, vp, vp, sz, vp]),
+        "tg_comm_destroy": (None, [vp]),
+        "tg_mapper_attach_comm": (i32, [vp, vp]),
+        "tg_mapper_result": (i32, [vp, vp, vp]),
+        "tg_mapper_result_topk": (i32, [vp, i32, vp, vp]),
+        "tg_topk_merge": (i32, [vp, vp, i64, i32, i64, i32, vp, vp, vp]),
+        "tg_mapper_project": (i32, [vp, vp]),
+        "tg_mapper_project_genes": (i32, [vp, vp, i64, i32, vp, i64, i32]),
+        "tg_csr_columns_to_dense": (i32, [vp, vp, vp, i64, i32, i32, vp, i64, vp]),
+        "tg_sparse_map_query_bytes": (i32, [i64, i64, i64, P(sz)]),
+        "tg_sparse_map_build": (i32, [vp, vp, vp, i64, i64, i64, vp, vp]),
+        "tg_sparse_map_project": (i32, [vp, i64, i64, i64, vp, i64, i32, vp, i64, vp]),
+        "tg_debug_sparse_map_layout": (i32, [i64, i64, P(i64)]),
+        "tg_consistency_query_bytes": (i32, [i32, i64, P(sz)]),
+        "tg_mapper_consistency": (i32, [P(vp), i32, vp, vp, vp, vp, vp]),
+        "tg_planes_consistency": (i32, planes),
+        "tg_debug_planes_consistency": (i32, planes + [i32]),
+        "tg_gene_scores_query_bytes": (i32, [i64, i32, P(sz)]),
+        "tg_gene_scores": (i32, [vp, i64, vp, i64, i64, i32, vp, vp, vp, vp]),
+        "tg_batch_query_bytes": (sz, [i32]),
+        "tg_batch_create": (i32, [P(vp), i32, vp, P(vp)]),
+        "tg_batch_step": (i32, [vp, i32, f32, P(vp), i32]),
+        "tg_batch_destroy": (None, [vp]),
+        "tg_csr_gather_columns": (i32, [vp, vp, vp, i64, vp, i32, vp, i64, vp]),
+        "tg_row_sums": (i32, [vp, i64, i32, vp, vp, i64, vp, i32, vp]),
+        "tg_cluster_aggregate": (i32, [vp, i64, i32, vp, vp, i32, i32, vp, i64, vp]),
+        "tg_init_logits_normal": (i32, [vp, i64, i64, i64, ct.c_uint64, i64, i64, vp]),
+        "tg_mapper_state": (i32, [vp, P(vp), P(vp), P(vp), P(i32), P(i64)]),
+        "tg_mapper_set_step": (i32, [vp, i64]),
+        "tg_mapper_effective_precision": (i32, [vp]),
+        "tg_mapper_filter_state": (i32, [vp, P(vp), P(i32)]),
+        "tg_mapper_validate": (i32, [vp, vp]),
+        "tg_mapper_profile": (i32, [vp, i32]),
+        "tg_mapper_profile_read": (i32, [vp, ct.c_char_p, sz, P(f32), P(i32), i32, P(i32)]),
+    }
+
+
+SIGNATURES = _signatures()
+EXPORTS = [name for name in SIGNATURES if not name.startswith("tg_debug_")]     # what include/tangram_hip.h declares
+
+
 def _declare(lib):
-    vp, i32, f32 = ct.c_void_p, ct.c_int, ct.c_float
-    lib.tg_abi_version.restype = i32
-    lib.tg_last_error.restype = ct.c_char_p
-    lib.tg_query_sizes.argtypes = [ct.POINTER(TgConfig), ct.POINTER(TgSizes)]
-    lib.tg_mapper_create.argtypes = [ct.POINTER(TgConfig), ct.POINTER(TgInputs), vp, vp, vp, ct.POINTER(vp)]
-    lib.tg_mapper_destroy.argtypes = [vp]
-    lib.tg_mapper_destroy.restype = None
-    lib.tg_mapper_step.argtypes = [vp, i32, f32, vp, i32]
-    lib.tg_comm_create_callbacks.argtypes = [i32, i32, ALL_REDUCE_FN, ALL_GATHER_FN, vp, ct.POINTER(vp)]
-    lib.tg_comm_rccl_unique_id.argtypes = [ct.c_char_p, vp]
-    lib.tg_comm_create_rccl.argtypes = [ct.c_char_p, vp, i32, i32, ct.POINTER(vp)]
-    lib.tg_comm_peer_create.argtypes = [i32, i32, ct.c_size_t, i32, vp, ct.POINTER(vp)]
-    lib.tg_comm_peer_create_stepped.argtypes = [i32, i32, ct.c_size_t, ct.c_size_t, i32, i32, vp, ct.POINTER(vp)]
-    lib.tg_comm_peer_connect.argtypes = [vp, vp]
-    lib.tg_comm_peer_status.argtypes = [vp, ct.POINTER(i32)]
-    lib.tg_comm_peer_set_timeout_ms.argtypes = [vp, ct.c_double]
-    lib.tg_comm_all_reduce_sum.argtypes = [vp, vp, ct.c_size_t, vp]
-    lib.tg_comm_all_gather.argtypes = [vp, vp, vp, ct.c_size_t, vp]
-    for name in ("tg_comm_peer_create", "tg_comm_peer_create_stepped", "tg_comm_peer_connect", "tg_comm_peer_status", "tg_comm_peer_set_timeout_ms", "tg_comm_all_reduce_sum",
-                 "tg_comm_all_gather"):
-        getattr(lib, name).restype = i32
-    lib.tg_comm_destroy.argtypes = [vp]
-    lib.tg_comm_destroy.restype = None
-    lib.tg_mapper_attach_comm.argtypes = [vp, vp]
-    lib.tg_mapper_result.argtypes = [vp, vp, vp]
-    lib.tg_mapper_result_topk.argtypes = [vp, ct.c_int32, vp, vp]
-    lib.tg_topk_merge.argtypes = [vp, vp, ct.c_int64, ct.c_int32, ct.c_int64, ct.c_int32, vp, vp, vp]
-    lib.tg_mapper_result_topk.restype = lib.tg_topk_merge.restype = i32
-    lib.tg_mapper_project.argtypes = [vp, vp]
-    lib.tg_mapper_project_genes.argtypes = [vp, vp, ct.c_int64, i32, vp, ct.c_int64, i32]
-    lib.tg_csr_columns_to_dense.argtypes = [vp, vp, vp, ct.c_int64, i32, i32, vp, ct.c_int64, vp]
-    lib.tg_csr_columns_to_dense.restype = i32
-    lib.tg_sparse_map_query_bytes.argtypes = [ct.c_int64, ct.c_int64, ct.c_int64, ct.POINTER(ct.c_size_t)]
-    lib.tg_sparse_map_build.argtypes = [vp, vp, vp, ct.c_int64, ct.c_int64, ct.c_int64, vp, vp]
-    lib.tg_sparse_map_project.argtypes = [vp, ct.c_int64, ct.c_int64, ct.c_int64, vp, ct.c_int64, ct.c_int32, vp, ct.c_int64, vp]
-    lib.tg_debug_sparse_map_layout.argtypes = [ct.c_int64, ct.c_int64, ct.POINTER(ct.c_int64)]
-    for name in ("tg_sparse_map_query_bytes", "tg_sparse_map_build", "tg_sparse_map_project", "tg_debug_sparse_map_layout"):
-        getattr(lib, name).restype = i32
-    lib.tg_consistency_query_bytes.argtypes = [ct.c_int32, ct.c_int64, ct.POINTER(ct.c_size_t)]
-    lib.tg_mapper_consistency.argtypes = [ct.POINTER(vp), ct.c_int32, vp, vp, vp, vp, vp]
-    lib.tg_planes_consistency.argtypes = [ct.POINTER(vp), ct.c_int32, ct.c_int64, ct.c_int64, ct.c_int64, vp, vp, vp, vp, vp, vp]
-    lib.tg_debug_planes_consistency.argtypes = lib.tg_planes_consistency.argtypes + [ct.c_int32]
-    for name in ("tg_consistency_query_bytes", "tg_mapper_consistency", "tg_planes_consistency", "tg_debug_planes_consistency"):
-        getattr(lib, name).restype = i32
-    lib.tg_gene_scores_query_bytes.argtypes = [ct.c_int64, ct.c_int32, ct.POINTER(ct.c_size_t)]
-    lib.tg_gene_scores.argtypes = [vp, ct.c_int64, vp, ct.c_int64, ct.c_int64, ct.c_int32, vp, vp, vp, vp]
-    lib.tg_gene_scores_query_bytes.restype = lib.tg_gene_scores.restype = i32
-    lib.tg_batch_query_bytes.argtypes = [i32]
-    lib.tg_batch_query_bytes.restype = ct.c_size_t
-    lib.tg_batch_create.argtypes = [ct.POINTER(vp), i32, vp, ct.POINTER(vp)]
-    lib.tg_batch_create.restype = i32
-    lib.tg_batch_step.argtypes = [vp, i32, f32, ct.POINTER(vp), i32]
-    lib.tg_batch_step.restype = i32
-    lib.tg_batch_destroy.argtypes = [vp]
-    lib.tg_batch_destroy.restype = None
-    lib.tg_csr_gather_columns.argtypes = [vp, vp, vp, ct.c_int64, vp, i32, vp, ct.c_int64, vp]
-    lib.tg_row_sums.argtypes = [vp, ct.c_int64, i32, vp, vp, ct.c_int64, vp, i32, vp]
-    lib.tg_cluster_aggregate.argtypes = [vp, ct.c_int64, i32, vp, vp, i32, i32, vp, ct.c_int64, vp]
-    lib.tg_init_logits_normal.argtypes = [vp, ct.c_int64, ct.c_int64, ct.c_int64, ct.c_uint64, ct.c_int64, ct.c_int64, vp]
-    for name in ("tg_csr_gather_columns", "tg_row_sums", "tg_cluster_aggregate", "tg_init_logits_normal"):
-        getattr(lib, name).restype = i32
-    lib.tg_mapper_state.argtypes = [vp, ct.POINTER(vp), ct.POINTER(vp), ct.POINTER(vp), ct.POINTER(ct.c_int32),
-                                    ct.POINTER(ct.c_int64)]
-    lib.tg_mapper_set_step.argtypes = [vp, ct.c_int64]
-    lib.tg_mapper_effective_precision.argtypes = [vp]
-    lib.tg_mapper_effective_precision.restype = i32
-    lib.tg_mapper_filter_state.argtypes = [vp, ct.POINTER(vp), ct.POINTER(ct.c_int32)]
-    lib.tg_mapper_filter_state.restype = i32
-    lib.tg_mapper_validate.argtypes = [vp, vp]
-    lib.tg_mapper_profile.argtypes = [vp, i32]
-    lib.tg_mapper_profile_read.argtypes = [vp, ct.c_char_p, ct.c_size_t, ct.POINTER(ct.c_float), ct.POINTER(i32), i32,
-                                           ct.POINTER(i32)]
-    for name in ("tg_query_sizes", "tg_mapper_create", "tg_mapper_step", "tg_comm_create_callbacks", "tg_comm_rccl_unique_id",
-                 "tg_comm_create_rccl", "tg_mapper_attach_comm", "tg_mapper_result", "tg_mapper_project", "tg_mapper_project_genes",
-                 "tg_mapper_state", "tg_mapper_set_step", "tg_mapper_profile", "tg_mapper_profile_read", "tg_mapper_validate"):
-        getattr(lib, name).restype = i32
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     return lib
-
-
-EXPORTS = ["tg_abi_version", "tg_last_error", "tg_query_sizes", "tg_mapper_create", "tg_mapper_destroy",
-           "tg_mapper_step", "tg_comm_create_callbacks", "tg_comm_rccl_unique_id", "tg_comm_create_rccl", "tg_comm_peer_create", "tg_comm_peer_create_stepped", "tg_comm_peer_connect", "tg_comm_peer_status", "tg_comm_peer_set_timeout_ms",
-           "tg_comm_all_reduce_sum", "tg_comm_all_gather", "tg_comm_destroy",
-           "tg_mapper_attach_comm", "tg_mapper_result", "tg_mapper_result_topk", "tg_topk_merge",
-           "tg_mapper_project", "tg_mapper_project_genes", "tg_csr_columns_to_dense", "tg_sparse_map_query_bytes", "tg_sparse_map_build",
-           "tg_sparse_map_project", "tg_consistency_query_bytes", "tg_mapper_consistency", "tg_planes_consistency", "tg_gene_scores_query_bytes", "tg_gene_scores", "tg_csr_gather_columns", "tg_row_sums",
-           "tg_cluster_aggregate", "tg_batch_query_bytes", "tg_batch_create", "tg_batch_step", "tg_batch_destroy", "tg_mapper_state", "tg_mapper_set_step",
-           "tg_mapper_filter_state", "tg_mapper_profile",
-           "tg_mapper_profile_read", "tg_mapper_validate", "tg_init_logits_normal", "tg_mapper_effective_precision"]
 
 
 def lib():

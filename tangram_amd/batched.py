@@ -22,7 +22,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import torch
 
-from . import _capi
+from . import _capi, _device
 
 
 class MapperBatch:
@@ -159,7 +159,7 @@ def train_many(builders, num_epochs, learning_rate=0.1, max_concurrent=4, device
     results, mappers = [None] * n, [None] * n
     val_each = train_kwargs.get("val_each")
     if batched and set(train_kwargs) <= {"val_each"}:
-        with (torch.cuda.device(device) if device.type == "cuda" else _null()):
+        with _device.current(device):
             for i in range(n):
                 mappers[i] = builders[i]()
             groups = {}
@@ -184,7 +184,7 @@ def train_many(builders, num_epochs, learning_rate=0.1, max_concurrent=4, device
         _train_on_streams(sorted(rest), mappers, results, device, num_epochs, learning_rate, max_concurrent, train_kwargs)
         return results, mappers
     streams = {}
-    with (torch.cuda.device(device) if device.type == "cuda" else _null()):
+    with _device.current(device):
         for i in range(n):
             if device.type == "cuda":                           # the library binds a handle to the stream it is created on
                 streams[i] = torch.cuda.Stream(device=device)
@@ -217,11 +217,3 @@ def _train_on_streams(idx, mappers, results, device, num_epochs, learning_rate, 
     with ThreadPoolExecutor(max_workers=max(1, int(max_concurrent))) as pool:
         for f in [pool.submit(work, i) for i in idx]:
             f.result()
-
-
-class _null:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False

@@ -51,8 +51,8 @@ def cv_data_gen(adata_sc, adata_sp, cv_mode="loo"):
 
 
 import logging
-from contextlib import nullcontext as _nullcontext
 
+from . import _device
 from .batched import BATCH_MAX_ELEMENTS
 
 
@@ -249,7 +249,7 @@ def cross_val(
         parts = [None] * world
         # (on the NCCL backend all_gather_object stages through torch.cuda.current_device(), not through `device`: make them agree,
         #  else every rank of a job that never called torch.cuda.set_device stages on cuda:0)
-        with (torch.cuda.device(device) if device.type == "cuda" else _nullcontext()):
+        with _device.current(device):
             dist.all_gather_object(parts, records, group=group)
         records = {k: v for part in parts for k, v in part.items()}
     test_genes_list, test_pred_list, test_score_list, train_score_list, test_df_list = [], [], [], [], []

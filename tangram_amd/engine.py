@@ -7,7 +7,8 @@ import ctypes as ct
 import numpy as np
 import torch
 
-from . import _capi
+from . import _capi, _device
+from .preprocess import DeviceCSR
 
 
 def _csr_pair(mat, n, device):
@@ -42,11 +43,7 @@ class HipMapperEngine:
                  bwd_tile=0, spot_offset=0, s_exact=False,
                  target_count=0.0, betas=(0.9, 0.999), eps=1e-8,
                  voxel_weights=None, neighborhood_filter=None, ct_encode=None, spatial_weights=None):
-        self.device = torch.device(device)
-        if self.device.type != "cuda" and not _capi.is_emulated():
-            raise RuntimeError(f"tangram_amd runs on a HIP device only (got device={device!r}); there is no CPU path")
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _device.check_device(device)
         if precision not in _capi.PRECISIONS:
             raise ValueError(f"gemm precision must be one of {sorted(_capi.PRECISIONS)}")
         self._lib = _capi.lib()
@@ -137,7 +134,7 @@ class HipMapperEngine:
         handle = ct.c_void_p()
         # the stream every call of this handle is enqueued on (the library binds to it at create())
         self._torch_stream = torch.cuda.current_stream(self.device) if self.device.type == "cuda" else None
-        self._hip_stream = self._stream()
+        self._hip_stream = _device.stream(self.device)
         self._call(self._lib.tg_mapper_create, ct.byref(cfg), ct.byref(inp), self.state.data_ptr(),
                    self.workspace.data_ptr(), self._hip_stream, ct.byref(handle))
         self._h = handle
@@ -154,11 +151,6 @@ class HipMapperEngine:
         self._scratch_row = torch.zeros(_capi.H_NTERMS, dtype=torch.float32, device=self.device)
 
     # -- plumbing ---------------------------------------------------------------------------------
-    def _stream(self):
-        if self.device.type == "cuda":
-            return ct.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        return None
-
     def _sync(self):
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
@@ -269,7 +261,7 @@ class HipMapperEngine:
         """softmax(M)^T S_all for ANY gene set -> [V, K_all] device tensor; the C x V mapping never leaves the GPU
         (reference: `adata_map.X.T @ adata_sc.X`, utils.py:366-368).  S_all: [C, K_all] float32 on this device, a host array,
         or a scipy.sparse matrix -- then the CSR arrays are uploaded once and every block of genes is expanded on the device
-        (tg_csr_columns_to_dense) instead of `adata_sc.X.toarray()` on the host (utils.py:364-365)."""
+        (preprocess.DeviceCSR.columns_into) instead of `adata_sc.X.toarray()` on the host (utils.py:364-365)."""
         if hasattr(S_all, "tocsr") and not isinstance(S_all, torch.Tensor):
             return self._project_genes_csr(S_all.tocsr(), unfiltered)
         S_all = torch.as_tensor(S_all)
@@ -287,19 +279,14 @@ class HipMapperEngine:
     def _project_genes_csr(self, csr, unfiltered):
         if csr.shape[0] != self.C:
             raise ValueError("S_all must be [n_cells, n_genes] with the mapper's cells")
-        if not csr.has_canonical_format:                             # one entry per (row, column), on a COPY: `tocsr()` of a CSR
-            csr = csr.copy()                                         # matrix is the caller's own object (adata_sc.X must not change)
-            csr.sum_duplicates()
+        csr = DeviceCSR(csr, self.device)
         n = int(csr.shape[1])
-        indptr = torch.as_tensor(np.asarray(csr.indptr, dtype=np.int64), device=self.device)
-        indices = torch.as_tensor(np.asarray(csr.indices, dtype=np.int32), device=self.device)
-        data = torch.as_tensor(np.asarray(csr.data, dtype=np.float32), device=self.device)
         out = torch.empty((self.V, n), dtype=torch.float32, device=self.device)
         block = torch.empty((self.C, min(self.K, n)), dtype=torch.float32, device=self.device)
+        expand = lambda fn, *args: self._call(fn, *args, self._hip_stream, tensors=(csr.indptr, csr.indices, csr.data, block))  # noqa: E731
         for k0 in range(0, n, self.K):
             kc = min(self.K, n - k0)
-            self._call(self._lib.tg_csr_columns_to_dense, indptr.data_ptr(), indices.data_ptr(), data.data_ptr(), self.C, k0, kc,
-                       block.data_ptr(), int(block.stride(0)), self._hip_stream, tensors=(indptr, indices, data, block))
+            csr.columns_into(k0, kc, block, launch=expand)
             self._call(self._lib.tg_mapper_project_genes, self._h, block.data_ptr(), int(block.stride(0)), kc,
                        out.data_ptr() + 4 * k0, n, 1 if unfiltered else 0, tensors=(block, out))
         return out

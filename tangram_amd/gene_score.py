@@ -11,13 +11,12 @@ gives the same bits in any block of any call.  Everything goes through the C ABI
 """
 from __future__ import annotations
 
-import ctypes as ct
-
 import numpy as np
 import torch
 
 from . import _capi
-from .preprocess import DeviceCSR, _call, _check_device, _stream
+from ._device import call, check_device, pitch, stream, workspace
+from .preprocess import DeviceCSR
 
 
 def _plane(x, device, name):
@@ -30,19 +29,13 @@ def _plane(x, device, name):
     return x
 
 
-def _pitch(x):
-    return int(x.stride(0)) if x.shape[0] > 1 else max(int(x.stride(0)), int(x.shape[1]))
-
-
 class GeneScorer:
     """Scores planes of `n_spots` rows and at most `max_genes` columns on `device`; nothing is allocated per call."""
 
     def __init__(self, n_spots, max_genes, device):
-        self.device = _check_device(device)
+        self.device = check_device(device)
         self.n_spots, self.max_genes = int(n_spots), int(max_genes)
-        nbytes = ct.c_size_t()
-        _capi.check(_capi.lib().tg_gene_scores_query_bytes(self.n_spots, self.max_genes, ct.byref(nbytes)))
-        self.workspace = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+        self.workspace = workspace(_capi.lib().tg_gene_scores_query_bytes, self.n_spots, self.max_genes, device=self.device)
 
     def score_into(self, pred, meas, score=None, moments=None):
         """pred, meas: float32 [n_spots, n] device tensors with unit column stride (views with a pitch are taken as they are);
@@ -58,9 +51,9 @@ class GeneScorer:
         for t, shape, name in ((score, (n,), "score"), (moments, (3, n), "moments")):
             if t is not None and (t.dtype != torch.float64 or t.device != self.device or tuple(t.shape) != shape or not t.is_contiguous()):
                 raise ValueError(f"{name} must be a contiguous float64 tensor of shape {shape} on {self.device}")
-        _call(self.device, _capi.lib().tg_gene_scores, pred.data_ptr() or None, _pitch(pred), meas.data_ptr() or None, _pitch(meas),
-              self.n_spots, n, self.workspace.data_ptr(), moments.data_ptr() if moments is not None else None,
-              score.data_ptr() if score is not None else None, _stream(self.device))
+        call(self.device, _capi.lib().tg_gene_scores, pred.data_ptr() or None, pitch(pred), meas.data_ptr() or None, pitch(meas),
+             self.n_spots, n, self.workspace.data_ptr(), moments.data_ptr() if moments is not None else None,
+             score.data_ptr() if score is not None else None, stream(self.device))
 
 
 def gene_scores(pred, meas, *, moments=False, device=None):
@@ -72,7 +65,7 @@ def gene_scores(pred, meas, *, moments=False, device=None):
         device = next((t.device for t in (pred, meas) if isinstance(t, torch.Tensor) and t.device.type == "cuda"), None)
         if device is None:
             device = next((t.device for t in (pred, meas) if isinstance(t, torch.Tensor)), torch.device("cuda:0"))
-    device = _check_device(device)
+    device = check_device(device)
     if tuple(pred.shape) != tuple(meas.shape):
         raise ValueError(f"pred is {tuple(pred.shape)}, meas is {tuple(meas.shape)}: the two planes must have the same shape")
     pred, meas = _plane(pred, device, "pred"), _plane(meas, device, "meas")
@@ -86,17 +79,15 @@ def gene_scores(pred, meas, *, moments=False, device=None):
 
 class GeneBlocks:
     """The gene columns `idx` (in that order) of the matrix X [n_obs, n_vars] -- dense, or scipy-sparse: then the selection is uploaded
-    once as CSR and every block is expanded on the device (tg_csr_columns_to_dense).  `fill(k0, kc, out)` writes the columns
+    once as CSR and every block is expanded on the device (DeviceCSR.columns_into).  `fill(k0, kc, out)` writes the columns
     k0 .. k0 + kc of the selection into the float32 device tensor `out[:, :kc]`."""
 
     def __init__(self, X, idx, device):
-        self.device = _check_device(device)
+        self.device = check_device(device)
         self.idx = np.asarray(idx, dtype=np.int64)
-        self.n_obs = int(X.shape[0])
         self.csr = self.dense = None
         if hasattr(X, "tocsr") and not isinstance(X, torch.Tensor):
-            sel = X.tocsr()[:, self.idx]
-            self.csr = DeviceCSR(sel, self.device) if sel.nnz else "empty"     # (an all-zero selection: no NULL arrays for the library)
+            self.csr = DeviceCSR(X.tocsr()[:, self.idx], self.device)          # the columns are selected on the host, before the upload
         else:
             self.dense = X
 
@@ -108,10 +99,6 @@ class GeneBlocks:
                 view.copy_(self.dense[:, torch.as_tensor(cols, device=self.dense.device)])
             else:
                 view.copy_(torch.as_tensor(np.ascontiguousarray(np.asarray(self.dense)[:, cols], dtype=np.float32)))
-        elif self.csr == "empty":
-            view.zero_()
         else:
-            c = self.csr
-            _call(self.device, _capi.lib().tg_csr_columns_to_dense, c.indptr.data_ptr(), c.indices.data_ptr(), c.data.data_ptr(), self.n_obs,
-                  int(k0), int(kc), out.data_ptr(), _pitch(out), _stream(self.device))
+            self.csr.columns_into(k0, kc, out)
         return view

@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _capi
+from ._device import call, check_device, stream, workspace
 
 METRICS = ("cell_map_consistency", "cell_map_agreement", "cell_map_certainty", "gene_expr_consistency", "gene_expr_correctness")
 _FLAT_COLS = 8192          # row length `pearson_corr` re-cuts narrow contiguous planes to (a row is one workgroup's work)
@@ -43,9 +44,7 @@ def _device_of(x, device):
 def _planes(cube, device):
     """`cube` (r, i, j) -- a host array, a device tensor or a list of r planes -- as r float32 device tensors [i, j] with unit
     column stride and one common row pitch."""
-    dev = _device_of(cube, device)
-    if dev.type != "cuda" and not _capi.is_emulated():
-        raise RuntimeError(f"tangram_amd runs on a HIP device only (got device={str(dev)!r}); there is no CPU path")
+    dev = check_device(_device_of(cube, device))
     if isinstance(cube, (list, tuple)):
         planes = [p if isinstance(p, torch.Tensor) else torch.as_tensor(np.asarray(p, dtype=np.float32)) for p in cube]
     else:
@@ -74,9 +73,7 @@ def planes_consistency(planes, pearson=True, vote=True, consensus=True, votes=Fa
     lib = _capi.lib()
     r = len(planes)
     n_rows, n_cols = (int(x) for x in planes[0].shape)
-    nbytes = ct.c_size_t()
-    _capi.check(lib.tg_consistency_query_bytes(r, n_rows, ct.byref(nbytes)))
-    ws = torch.empty(max(int(nbytes.value), 8), dtype=torch.uint8, device=dev)
+    ws = workspace(lib.tg_consistency_query_bytes, r, n_rows, device=dev, min_bytes=8)
     out = {}
     if pearson and r > 1:
         out["pearson"] = torch.empty(r * (r - 1) // 2, dtype=torch.float64, device=dev)
@@ -89,15 +86,8 @@ def planes_consistency(planes, pearson=True, vote=True, consensus=True, votes=Fa
     ptr = lambda k: out[k].data_ptr() if k in out else None
     arr = (ct.c_void_p * r)(*[p.data_ptr() for p in planes])
     fn, tail = (lib.tg_planes_consistency, ()) if _max_parts is None else (lib.tg_debug_planes_consistency, (int(_max_parts),))
-    if dev.type == "cuda":
-        with torch.cuda.device(dev):
-            stream = ct.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            rc = fn(arr, r, n_rows, n_cols, int(planes[0].stride(0)), ws.data_ptr(), ptr("pearson"), ptr("vote_entropy"),
-                    ptr("consensus_entropy"), ptr("votes"), stream, *tail)
-    else:
-        rc = fn(arr, r, n_rows, n_cols, int(planes[0].stride(0)), ws.data_ptr(), ptr("pearson"), ptr("vote_entropy"), ptr("consensus_entropy"),
-                ptr("votes"), None, *tail)
-    _capi.check(rc)
+    call(dev, fn, arr, r, n_rows, n_cols, int(planes[0].stride(0)), ws.data_ptr(), ptr("pearson"), ptr("vote_entropy"),
+         ptr("consensus_entropy"), ptr("votes"), stream(dev), *tail)
     return out
 
 
@@ -157,9 +147,7 @@ def mapper_consistency(mappers, votes=False):
         raise ValueError("no mapper")
     e0 = engines[0]
     lib, dev, r = e0._lib, e0.device, len(engines)
-    nbytes = ct.c_size_t()
-    _capi.check(lib.tg_consistency_query_bytes(r, e0.C, ct.byref(nbytes)))
-    ws = torch.empty(max(int(nbytes.value), 8), dtype=torch.uint8, device=dev)
+    ws = workspace(lib.tg_consistency_query_bytes, r, e0.C, device=dev, min_bytes=8)
     out = {"vote_entropy": torch.empty(e0.C, dtype=torch.float32, device=dev),
            "consensus_entropy": torch.empty(e0.C, dtype=torch.float32, device=dev)}
     if r > 1:

@@ -11,48 +11,40 @@ Everything goes through the C ABI (tg_csr_gather_columns, tg_row_sums, tg_cluste
 """
 from __future__ import annotations
 
-import ctypes as ct
-
 import numpy as np
 import torch
 
 from . import _capi
-
-
-def _stream(device):
-    return ct.c_void_p(torch.cuda.current_stream(device).cuda_stream) if device.type == "cuda" else None
-
-
-def _check_device(device):
-    device = torch.device(device)
-    if device.type != "cuda" and not _capi.is_emulated():
-        raise RuntimeError(f"tangram_amd runs on a HIP device only (got device={device!r}); there is no CPU path")
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    return device
-
-
-def _call(device, fn, *args):
-    if device.type == "cuda":
-        with torch.cuda.device(device):
-            return _capi.check(fn(*args))
-    return _capi.check(fn(*args))
+from ._device import call as _call, check_device as _check_device, pitch, stream as _stream     # (the old names stay importable)
 
 
 class DeviceCSR:
-    """A scipy.sparse matrix uploaded once: int64 indptr, int32 indices, float32 data (canonical: sorted, no duplicates)."""
+    """A scipy.sparse matrix uploaded once: int64 indptr, int32 indices, float32 data (canonical: sorted, no duplicates).  The one
+    place that canonicalises (on a copy) and uploads a gene matrix; `columns_into` expands blocks of its columns on the device."""
 
     def __init__(self, X, device):
         import scipy.sparse as sp
         self.device = _check_device(device)
         csr = X.tocsr() if sp.issparse(X) else sp.csr_matrix(np.asarray(X))
         if not csr.has_canonical_format:
-            csr = csr.copy()                       # never edit the caller's matrix
+            csr = csr.copy()                       # never edit the caller's matrix (`tocsr()` of a CSR matrix is that very object)
             csr.sum_duplicates()
         self.shape = csr.shape
         self.indptr = torch.as_tensor(np.asarray(csr.indptr, dtype=np.int64), device=self.device)
         self.indices = torch.as_tensor(np.asarray(csr.indices, dtype=np.int32), device=self.device)
         self.data = torch.as_tensor(np.asarray(csr.data, dtype=np.float32), device=self.device)
+
+    def columns_into(self, k0, kc, out, launch=None):
+        """out[:, :kc] = the columns k0 .. k0 + kc as dense float32 (tg_csr_columns_to_dense); `out`: a float32 device tensor of
+        shape[0] rows with unit column stride.  An all-zero matrix zero-fills without the library (it takes no NULL arrays).
+        `launch(fn, *args)`: how a `tg_mapper` handle enqueues the call on its own stream; default: the caller's current stream."""
+        if self.data.numel() == 0:
+            out[:, :kc].zero_()
+            return
+        if launch is None:
+            launch = lambda fn, *args: _call(self.device, fn, *args, _stream(self.device))          # noqa: E731
+        launch(_capi.lib().tg_csr_columns_to_dense, self.indptr.data_ptr(), self.indices.data_ptr(), self.data.data_ptr(),
+               int(self.shape[0]), int(k0), int(kc), out.data_ptr(), pitch(out))
 
 
 def gather_training_genes(X, col_index, device):

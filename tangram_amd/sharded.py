@@ -38,16 +38,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import _capi
+from . import _capi, _device
 from .engine import HipMapperEngine
-
-
-class _Null:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
 
 
 class DistComm:
@@ -209,8 +201,7 @@ class ShardedMapperEngine:
         colocated = self._colocated_ranks(dev)
         self.mailbox_bytes = 256 + 2 * self.world * (cap + step + 1024) * 8      # (reported: it is the one allocation outside tg_query_sizes)
         handle, ok, why = ct.c_void_p(), True, ""
-        ctx = torch.cuda.device(dev) if dev.type == "cuda" else _Null()
-        with ctx:
+        with _device.current(dev):
             buf = ct.create_string_buffer(64)
             try:
                 _capi.check(lib.tg_comm_peer_create_stepped(self.world, self.rank, cap, step, colocated, int(same), buf, ct.byref(handle)))
@@ -308,7 +299,7 @@ class ShardedMapperEngine:
         if self.transport != "peer" or not getattr(self, "_comm", None):
             return
         flag = ct.c_int(0)
-        with (torch.cuda.device(self.eng.device) if self.eng.device.type == "cuda" else _Null()):
+        with _device.current(self.eng.device):
             _capi.check(self.eng._lib.tg_comm_peer_status(self._comm, ct.byref(flag)))
         if flag.value:
             raise RuntimeError("tangram_amd: a peer-memory exchange timed out waiting for another rank (results are invalid)")

@@ -5,7 +5,7 @@ thresholded -- and the single-cell matrix S.  No mapper, no logits and no cells 
   SparseMap         the spot-major image of X, built once on the device (tg_sparse_map_build): per spot its (cell, value)
                     entries in ascending cell order, a pure function of X; `.project(S)` any number of times
   project_sparse    X.T @ S -> [n_spots, n_genes] float32 device tensor; S dense (host array or device tensor: one call) or
-                    scipy-sparse (uploaded once as CSR, expanded 1 024 genes at a time with tg_csr_columns_to_dense)
+                    scipy-sparse (uploaded once as a preprocess.DeviceCSR, expanded 1 024 genes at a time)
 
 Every output element is one fp32 fmaf chain from 0 over the entries of its spot in that order: the same bits on every call, for every
 alignment of S and for every split of the gene range.  The host checks the matrix (shape, index range, indptr) before anything is
@@ -19,7 +19,8 @@ import numpy as np
 import torch
 
 from . import _capi
-from .preprocess import _call, _check_device, _stream
+from ._device import call, check_device, pitch, stream, workspace
+from .preprocess import DeviceCSR
 
 GENE_BLOCK = 1024           # genes of a sparse S expanded at a time (there is no mapper K to borrow here)
 
@@ -51,21 +52,16 @@ class SparseMap:
     """The spot-major image of a cells x spots sparse mapping on `device`."""
 
     def __init__(self, X, device="cuda:0", n_cells=None):
-        self.device = _check_device(device)
+        self.device = check_device(device)
         csr = canonical_csr(X, n_cells)
         self.n_cells, self.n_spots = (int(n) for n in csr.shape)
         self.nnz = int(csr.nnz)
         lib = _capi.lib()
-        nbytes = ct.c_size_t()
-        _capi.check(lib.tg_sparse_map_query_bytes(self.n_cells, self.n_spots, self.nnz, ct.byref(nbytes)))
-        with (torch.cuda.device(self.device) if self.device.type == "cuda" else _Null()):
-            indptr = torch.as_tensor(np.asarray(csr.indptr, dtype=np.int64), device=self.device)
-            indices = torch.as_tensor(np.asarray(csr.indices, dtype=np.int32), device=self.device)
-            data = torch.as_tensor(np.asarray(csr.data, dtype=np.float32), device=self.device)
-            self.workspace = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
-            _call(self.device, lib.tg_sparse_map_build, indptr.data_ptr(), indices.data_ptr() or None, data.data_ptr() or None,
-                  self.n_cells, self.n_spots, self.nnz, self.workspace.data_ptr(), _stream(self.device))
-        self._csr_dev = (indptr, indices, data)      # (kept until the build has run: same stream as every later use)
+        self.workspace = workspace(lib.tg_sparse_map_query_bytes, self.n_cells, self.n_spots, self.nnz, device=self.device)
+        up = DeviceCSR(csr, self.device)
+        call(self.device, lib.tg_sparse_map_build, up.indptr.data_ptr(), up.indices.data_ptr() or None, up.data.data_ptr() or None,
+             self.n_cells, self.n_spots, self.nnz, self.workspace.data_ptr(), stream(self.device))
+        self._csr_dev = (up.indptr, up.indices, up.data)      # (kept until the build has run: same stream as every later use)
 
     def image(self):
         """(spot_ptr int64 [n_spots + 1], cell int32 [nnz], val float32 [nnz]): views of the workspace, no copy."""
@@ -83,9 +79,8 @@ class SparseMap:
                 raise ValueError(f"{name} must be a float32 [{rows}, n_genes] tensor on {self.device} with unit column stride")
         if S.shape[1] != out.shape[1]:
             raise ValueError("S and out differ in their number of genes")
-        _call(self.device, _capi.lib().tg_sparse_map_project, self.workspace.data_ptr(), self.n_cells, self.n_spots, self.nnz,
-              S.data_ptr() or None, int(S.stride(0)) if S.shape[0] > 1 else int(S.shape[1]), int(S.shape[1]),
-              out.data_ptr() or None, int(out.stride(0)) if out.shape[0] > 1 else int(out.shape[1]), _stream(self.device))
+        call(self.device, _capi.lib().tg_sparse_map_project, self.workspace.data_ptr(), self.n_cells, self.n_spots, self.nnz,
+             S.data_ptr() or None, pitch(S), int(S.shape[1]), out.data_ptr() or None, pitch(out), stream(self.device))
         return out
 
     def project(self, S_all):
@@ -107,34 +102,17 @@ class SparseMap:
     def _project_csr(self, csr):
         if csr.shape[0] != self.n_cells:
             raise ValueError("S_all must be [n_cells, n_genes] with the mapping's cells")
-        if not csr.has_canonical_format:             # one entry per (row, column), on a COPY (adata_sc.X must not change)
-            csr = csr.copy()
-            csr.sum_duplicates()
         n = int(csr.shape[1])
         out = torch.empty((self.n_spots, n), dtype=torch.float32, device=self.device)
         if out.numel() == 0:
             return out
-        lib = _capi.lib()
-        indptr = torch.as_tensor(np.asarray(csr.indptr, dtype=np.int64), device=self.device)
-        indices = torch.as_tensor(np.asarray(csr.indices, dtype=np.int32), device=self.device)
-        data = torch.as_tensor(np.asarray(csr.data, dtype=np.float32), device=self.device)
-        if data.numel() == 0:                        # (an all-zero S: nothing to expand, and no NULL arrays for the library)
-            return out.zero_()
+        csr = DeviceCSR(csr, self.device)
         block = torch.empty((self.n_cells, min(GENE_BLOCK, n)), dtype=torch.float32, device=self.device)
         for k0 in range(0, n, GENE_BLOCK):
             kc = min(GENE_BLOCK, n - k0)
-            _call(self.device, lib.tg_csr_columns_to_dense, indptr.data_ptr(), indices.data_ptr(), data.data_ptr(), self.n_cells, k0, kc,
-                  block.data_ptr(), int(block.stride(0)), _stream(self.device))
+            csr.columns_into(k0, kc, block)
             self.project_into(block[:, :kc], out[:, k0:k0 + kc])
         return out
-
-
-class _Null:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
 
 
 def project_sparse(X_csr, S_all, device="cuda:0"):

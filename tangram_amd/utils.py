@@ -98,50 +98,11 @@ def project_genes(adata_map, adata_sc, cluster_label=None, scale=True, *, mapper
     Unlike the reference (`sc.pp.filter_genes`, `var_names_make_unique` mutate the caller's AnnData in place, :351-357),
     only `adata_sc.var.index` is rewritten in place; the gene filter and `n_cells` land on a view."""
     adata_sc, S_all = _prepare_sc(adata_map, adata_sc, cluster_label, scale)
-    own = mapper is None
-    if truncated:
-        if not own:
-            raise ValueError("truncated=True projects the sparse adata_map.X itself: it cannot be combined with mapper=")
-        if not hasattr(adata_map.X, "tocsr"):
-            raise ValueError("truncated=True needs a sparse adata_map.X (the top_k= result); a dense mapping is projected without it")
-        from .sparse_project import SparseMap
-        X_space = SparseMap(adata_map.X, device, n_cells=S_all.shape[0]).project(S_all).cpu().numpy()      # :366, no renormalisation
-        adata_ge = _result(X_space, adata_map.var, adata_sc.var, adata_sc.uns)
-        training_genes = adata_map.uns["train_genes_df"].index.values
-        adata_ge.var["is_training"] = adata_ge.var.index.isin(training_genes)
-        return adata_ge
-    if own and hasattr(adata_map.X, "tocsr"):
-        raise ValueError("adata_map.X is sparse (map_cells_to_space(..., top_k=k) keeps each cell's k most probable spots only): "
-                         "project with the trained mapping instead -- map with keep_mapper=True and pass "
-                         "mapper=adata_map._tangram_amd_mapper -- or project the truncated matrix itself with truncated=True")
-    if own:
-        engine, rows = _projection_engine(adata_map, torch.device(device), gemm_precision)
-    else:
-        engine, rows = mapper._engine, None
-    if engine.C != S_all.shape[0]:
-        raise ValueError("The two AnnDatas need to have same `obs` index.")
-    if not own:
-        # the trained mapper projects through its own seam: on a spot-sharded run that gathers every rank's block of spots
-        # (mapper._engine alone is only the LOCAL shard); MapperConstrained: softmax(M) without the filter, like adata_map.X
-        from .mapping_optimizer import MapperConstrained
-        if isinstance(mapper, MapperConstrained):
-            X_space = mapper.project_genes_device(S_all, unfiltered=True)
-        else:
-            X_space = mapper.project_genes_device(S_all)
-        X_space = X_space.cpu().numpy()
-        adata_ge = _result(X_space, adata_map.var, adata_sc.var, adata_sc.uns)
-        training_genes = adata_map.uns["train_genes_df"].index.values
-        adata_ge.var["is_training"] = adata_ge.var.index.isin(training_genes)
-        return adata_ge
-    if rows is not None and np.abs(rows - 1.0).max() > 1e-6:                         # not row-stochastic: P^T S = (P / r)^T (r S)
-        if hasattr(S_all, "tocsr"):
-            import scipy.sparse as sp
-            S_all = (sp.diags(rows) @ S_all.tocsr()).tocsr()
-        else:
-            S_all = np.ascontiguousarray(S_all * rows[:, None], dtype=np.float32)
-    X_space = engine.project_genes(S_all, unfiltered=True).cpu().numpy()             # :366  (adata_map.X.T @ adata_sc.X)
-    if own:
-        engine.release()
+    route = _Route(adata_map, S_all.shape[0], mapper, truncated, device, gemm_precision)
+    try:
+        X_space = route.project(S_all).cpu().numpy()                                 # :366  (adata_map.X.T @ adata_sc.X)
+    finally:
+        route.release()
     adata_ge = _result(X_space, adata_map.var, adata_sc.var, adata_sc.uns)           # :367-369
     training_genes = adata_map.uns["train_genes_df"].index.values                    # :370-371
     adata_ge.var["is_training"] = adata_ge.var.index.isin(training_genes)
@@ -220,54 +181,68 @@ def compare_spatial_geneexp(adata_ge, adata_sp, adata_sc=None, genes=None, *, de
     return _score_frame(scores.cpu().numpy(), overlap_genes, adata_ge.var, adata_sp, adata_sc, genes)
 
 
-def _block_projection(adata_map, n_cells, mapper, truncated, device, gemm_precision):
-    """One of project_genes' three routes as `project(S_block [n_cells, kc] float32 device tensor) -> [n_spots, kc] device tensor`,
-    with its device, its number of spots and what to call when done.  The ValueError rules are those of project_genes."""
-    own = mapper is None
-    nothing = lambda: None                                                            # noqa: E731
-    if truncated:
-        if not own:
-            raise ValueError("truncated=True projects the sparse adata_map.X itself: it cannot be combined with mapper=")
-        if not hasattr(adata_map.X, "tocsr"):
-            raise ValueError("truncated=True needs a sparse adata_map.X (the top_k= result); a dense mapping is projected without it")
-        from .sparse_project import SparseMap
-        sm = SparseMap(adata_map.X, device, n_cells=n_cells)
-        scratch = {}
+class _Route:
+    """The route `project_genes` and `score_genes` take from their keywords, stated once: the mapping resident in HBM (`mapper=`, on
+    a spot-sharded run gathered across the ranks), a dense `adata_map.X` through an engine of its own, or the sparse `adata_map.X`
+    itself (`truncated=True`).  `project(S)` -> [n_spots, n_genes] float32 device tensor for S [n_cells, n_genes]: a host array, a
+    scipy-sparse matrix or a device block; `device`, `n_spots`; `release()` frees the engine made for a dense `adata_map.X`."""
 
-        def project(S_blk):
-            kc = int(S_blk.shape[1])
-            if "out" not in scratch or scratch["out"].shape[1] < kc:
-                scratch["out"] = torch.empty((sm.n_spots, kc), dtype=torch.float32, device=sm.device)
-            return sm.project_into(S_blk, scratch["out"][:, :kc])
-        return project, sm.device, sm.n_spots, nothing
-    if own and hasattr(adata_map.X, "tocsr"):
-        raise ValueError("adata_map.X is sparse (map_cells_to_space(..., top_k=k) keeps each cell's k most probable spots only): "
-                         "project with the trained mapping instead -- map with keep_mapper=True and pass "
-                         "mapper=adata_map._tangram_amd_mapper -- or project the truncated matrix itself with truncated=True")
-    if not own:
-        if getattr(mapper, "_sharded", None) is not None:
-            raise ValueError("score_genes does not take a spot-sharded mapper: every rank holds the moments of its own spots only, and "
-                             "their exchange is not available; project with project_genes and score with compare_spatial_geneexp")
-        engine = mapper._engine
+    def __init__(self, adata_map, n_cells, mapper, truncated, device, gemm_precision):
+        self._rows = self._engine = None
+        if truncated:
+            if mapper is not None:
+                raise ValueError("truncated=True projects the sparse adata_map.X itself: it cannot be combined with mapper=")
+            if not hasattr(adata_map.X, "tocsr"):
+                raise ValueError("truncated=True needs a sparse adata_map.X (the top_k= result); a dense mapping is projected without it")
+            from .sparse_project import SparseMap
+            sm = SparseMap(adata_map.X, device, n_cells=n_cells)                      # :366, no renormalisation
+            self.device, self.n_spots, self._project, self._sm, self._out = sm.device, sm.n_spots, self._truncated, sm, None
+            return
+        if mapper is None:
+            if hasattr(adata_map.X, "tocsr"):
+                raise ValueError("adata_map.X is sparse (map_cells_to_space(..., top_k=k) keeps each cell's k most probable spots only): "
+                                 "project with the trained mapping instead -- map with keep_mapper=True and pass "
+                                 "mapper=adata_map._tangram_amd_mapper -- or project the truncated matrix itself with truncated=True")
+            engine, rows = _projection_engine(adata_map, torch.device(device), gemm_precision)
+            self._engine = engine
+            if np.abs(rows - 1.0).max() > 1e-6:                                       # not row-stochastic: P^T S = (P / r)^T (r S)
+                self._rows = rows
+            self._project = lambda S: engine.project_genes(S, unfiltered=True)
+        else:
+            # the trained mapper projects through its own seam: on a spot-sharded run that gathers every rank's block of spots
+            # (mapper._engine alone is only the LOCAL shard); MapperConstrained: softmax(M) without the filter, like adata_map.X
+            from .mapping_optimizer import MapperConstrained
+            engine = mapper._engine
+            kw = dict(unfiltered=True) if isinstance(mapper, MapperConstrained) else {}
+            self._project = lambda S: mapper.project_genes_device(S, **kw)
+        self.device, self.n_spots = engine.device, engine.V
         if engine.C != n_cells:
+            self.release()
             raise ValueError("The two AnnDatas need to have same `obs` index.")
-        from .mapping_optimizer import MapperConstrained
-        if isinstance(mapper, MapperConstrained):                                     # softmax(M) without the filter, like adata_map.X
-            return (lambda S_blk: mapper.project_genes_device(S_blk, unfiltered=True)), engine.device, engine.V, nothing
-        return (lambda S_blk: mapper.project_genes_device(S_blk)), engine.device, engine.V, nothing
-    engine, rows = _projection_engine(adata_map, torch.device(device), gemm_precision)
-    if engine.C != n_cells:
-        engine.release()
-        raise ValueError("The two AnnDatas need to have same `obs` index.")
-    scale = None
-    if np.abs(rows - 1.0).max() > 1e-6:                                               # not row-stochastic: P^T S = (P / r)^T (r S)
-        scale = torch.as_tensor(rows, dtype=torch.float64, device=engine.device)[:, None]
 
-    def project(S_blk):
-        if scale is not None:
-            S_blk = (S_blk.double() * scale).float()
-        return engine.project_genes(S_blk, unfiltered=True)
-    return project, engine.device, engine.V, engine.release
+    def project(self, S):
+        if self._rows is not None:                       # the float32 value times the float64 row sum, rounded to float32 once
+            if hasattr(S, "tocsr") and not isinstance(S, torch.Tensor):
+                import scipy.sparse as sp
+                S = (sp.diags(self._rows) @ S.tocsr()).tocsr()
+            else:
+                S = torch.as_tensor(S).to(device=self.device, dtype=torch.float32)
+                S = (S.double() * torch.as_tensor(self._rows, device=self.device)[:, None]).float()
+        return self._project(S)
+
+    def _truncated(self, S):
+        sm = self._sm
+        if not (isinstance(S, torch.Tensor) and S.device == sm.device):
+            return sm.project(S)
+        kc = int(S.shape[1])                             # a device block (score_genes): the scratch is reused
+        if self._out is None or self._out.shape[1] < kc:
+            self._out = torch.empty((sm.n_spots, kc), dtype=torch.float32, device=sm.device)
+        return sm.project_into(S, self._out[:, :kc])
+
+    def release(self):
+        if self._engine is not None:
+            self._engine.release()
+            self._engine = None
 
 
 def score_genes(adata_map, adata_sc, adata_sp, cluster_label=None, scale=True, genes=None, *, mapper=None, truncated=False,
@@ -284,7 +259,11 @@ def score_genes(adata_map, adata_sc, adata_sp, cluster_label=None, scale=True, g
     from .gene_score import GeneBlocks, GeneScorer
     adata_sc_p, S_all = _prepare_sc(adata_map, adata_sc, cluster_label, scale)
     n_cells = int(S_all.shape[0])
-    project, dev, n_spots, done = _block_projection(adata_map, n_cells, mapper, truncated, device, gemm_precision)
+    if mapper is not None and not truncated and getattr(mapper, "_sharded", None) is not None:
+        raise ValueError("score_genes does not take a spot-sharded mapper: every rank holds the moments of its own spots only, and "
+                         "their exchange is not available; project with project_genes and score with compare_spatial_geneexp")
+    route = _Route(adata_map, n_cells, mapper, truncated, device, gemm_precision)
+    dev, n_spots = route.device, route.n_spots
     try:
         overlap_genes = _check_score_inputs(adata_sc_p.uns, adata_sp, genes)
         mu.annotate_gene_sparsity(adata_sp)
@@ -309,8 +288,8 @@ def score_genes(adata_map, adata_sc, adata_sp, cluster_label=None, scale=True, g
                     S_blk = pre.gather_training_genes(S_dev, cols, dev)
                 else:
                     S_blk = S_dev.index_select(1, torch.as_tensor(cols, dtype=torch.int64, device=dev))
-                scorer.score_into(project(S_blk), sp_.fill(k0, kc, meas), scores[k0:k0 + kc])
+                scorer.score_into(route.project(S_blk), sp_.fill(k0, kc, meas), scores[k0:k0 + kc])
         scores = scores.cpu().numpy()
     finally:
-        done()
+        route.release()
     return _score_frame(scores, overlap_genes, var_ge, adata_sp, adata_sc, genes)

@@ -532,3 +532,107 @@ def check_train_score_invariant(device):
     print(f"mean training score {score:.6f}, main_loss[-1] {last:.6f}")
     assert df["is_training"].sum() == v["n_train"]
     assert round(score, 3) == round(last, 3)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# project_genes' routes: one statement of the rules, one CSR upload, one rescaling
+# ------------------------------------------------------------------------------------------------------------------------------
+ROUTE_ERRORS = {       # the texts as the routes were first written, not read from the code under test
+    "truncated with mapper=": "truncated=True projects the sparse adata_map.X itself: it cannot be combined with mapper=",
+    "truncated with a dense X": "truncated=True needs a sparse adata_map.X (the top_k= result); a dense mapping is projected without it",
+    "sparse X without a mapper": "adata_map.X is sparse (map_cells_to_space(..., top_k=k) keeps each cell's k most probable spots only): "
+                                 "project with the trained mapping instead -- map with keep_mapper=True and pass "
+                                 "mapper=adata_map._tangram_amd_mapper -- or project the truncated matrix itself with truncated=True",
+    "obs index mismatch": "The two AnnDatas need to have same `obs` index.",
+}
+
+
+def check_route_errors(device):
+    """project_genes and score_genes refuse the same four situations with the same words."""
+    import tangram_amd as tg
+    from tangram_amd.anndata_lite import AnnDataLite
+    dense, _, _, kw_m = mapped(device, "mapper")
+    top = mapped(device, "truncated")[0]
+
+    def short(ad):
+        return AnnDataLite(ad.X[:-1], obs=ad.obs.iloc[:-1], var=ad.var.copy(), uns=ad.uns)
+
+    cases = {"truncated with mapper=": ("truncated", dict(truncated=True, mapper=kw_m["mapper"]), False),
+             "truncated with a dense X": ("mapper", dict(truncated=True), False),
+             "sparse X without a mapper": ("truncated", {}, False),
+             "obs index mismatch": ("mapper", {}, True)}
+    assert set(cases) == set(ROUTE_ERRORS)
+    for what, (route, kw, cut) in cases.items():
+        ad_map = top if route == "truncated" else dense
+        for fn in ("project_genes", "score_genes"):
+            _, ad_sc, ad_sp, _ = mapped(device, route)
+            ad_sc = short(ad_sc) if cut else ad_sc
+            args = (ad_map, ad_sc) + ((ad_sp,) if fn == "score_genes" else ())
+            with pytest.raises(ValueError) as e:
+                getattr(tg, fn)(*args, device=device, **kw)
+            assert str(e.value) == ROUTE_ERRORS[what], f"{fn}, {what}"
+
+
+def check_all_zero_sparse_block(device):
+    """An all-zero scipy-sparse block of adata_sc.X (empty index and data arrays) through the three users of the CSR upload: zeros,
+    and no complaint of the library about a NULL array."""
+    from tangram_amd import SparseMap
+    from tangram_amd.engine import HipMapperEngine
+    from tangram_amd.gene_score import GeneBlocks
+    C, V, K, n = 37, 21, 3, 7                                          # 7 genes: the engine expands blocks of K = 3, 3, 1
+    rng = np.random.default_rng(5)
+    Z = sp.csr_matrix((C, n), dtype=np.float32)
+    assert Z.nnz == 0 and Z.data.size == 0
+    eng = HipMapperEngine(rng.random((C, K), dtype=np.float32), rng.random((V, K), dtype=np.float32),
+                          rng.standard_normal((C, V)).astype(np.float32), device=device)
+    out = _np(eng.project_genes(Z))
+    eng.release()
+    assert out.shape == (V, n) and not out.any(), "HipMapperEngine.project_genes"
+    X = sp.random(C, V, density=0.2, random_state=3, format="csr", dtype=np.float32)
+    out = _np(SparseMap(X, device).project(Z))
+    assert out.shape == (V, n) and not out.any(), "SparseMap.project"
+    buf = torch.full((C, 5), 7.0, dtype=torch.float32, device=torch.device(device))
+    view = GeneBlocks(Z, np.arange(n), device).fill(2, 4, buf)
+    assert tuple(view.shape) == (C, 4) and not _np(view).any() and (_np(buf)[:, 4] == 7.0).all(), "GeneBlocks.fill"
+
+
+def check_unnormalised_dense_mapping(device, golden_dir):
+    """A dense adata_map.X whose rows sum to 0.5 .. 2 (P^T S = (P / r)^T (r S)): a dense host S, a scipy-sparse S and a device block
+    give the same bits.  The stored array is project_genes of the commit before the routes were merged, on the emulator: the
+    emulator reproduces its bits.  The GPU multiplies in another order: both are within 2^-14 |P|^T |S| of the exact product (bf16x3
+    keeps 16 significand bits of either operand and drops the low x low product: 3 x 2^-16 per product; 40 fp32 additions, 2^-24
+    each, and the fp32 exp / log of softmax(log P) fit in the remaining 2^-16), so they are within 2^-13 |P|^T |S| of each other."""
+    import os
+    import tangram_amd as tg
+    from tangram_amd import utils
+    from tangram_amd.anndata_lite import AnnDataLite
+    z = np.load(os.path.join(golden_dir, "unnormalised_dense_projection.npz"))
+    P, S, want = z["P"], z["S"], z["X_space"]
+    rows = P.sum(axis=1)
+    assert rows.min() < 0.7 and rows.max() > 1.5
+    C, V = P.shape
+    n = S.shape[1]
+    genes, cells = [f"g{i}" for i in range(n)], [f"c{i}" for i in range(C)]
+    got = {}
+    for form in ("dense host S", "scipy-sparse S"):
+        ad_map = AnnDataLite(P.copy(), obs=pd.DataFrame(index=cells), var=pd.DataFrame(index=[f"s{i}" for i in range(V)]),
+                             uns={"train_genes_df": pd.DataFrame(index=genes[:4])})
+        ad_sc = AnnDataLite(sp.csr_matrix(S) if form.startswith("scipy") else S.copy(), obs=pd.DataFrame(index=cells),
+                            var=pd.DataFrame(index=genes))
+        got[form] = np.asarray(tg.project_genes(ad_map, ad_sc, device=device).X)
+    route = utils._Route(ad_map, C, None, False, device, "bf16x3")
+    try:
+        got["device block"] = _np(route.project(torch.as_tensor(S, device=torch.device(device))))
+    finally:
+        route.release()
+    for form, x in got.items():
+        assert x.dtype == np.float32 and x.shape == want.shape
+        np.testing.assert_array_equal(x.view(np.uint32), got["dense host S"].view(np.uint32), err_msg=f"{form} against the dense host S")
+    x = got["dense host S"]
+    if torch.device(device).type == "cpu":
+        np.testing.assert_array_equal(x.view(np.uint32), want.view(np.uint32), err_msg="against the stored projection")
+    else:
+        bound = 2.0 ** -13 * (np.abs(P.astype(np.float64)).T @ np.abs(S.astype(np.float64)))
+        err = np.abs(x.astype(np.float64) - want)
+        print(f"unnormalised dense mapping: max error / bound against the stored projection {(err / bound).max():.4f}")
+        assert (err <= bound).all()

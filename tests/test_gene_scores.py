@@ -70,3 +70,15 @@ def test_reference_holds_the_train_score_invariant():
 
 def test_train_score_invariant(sim):
     gc.check_train_score_invariant(DEV)
+
+
+def test_route_errors_are_the_same_in_project_genes_and_score_genes(sim):
+    gc.check_route_errors(DEV)
+
+
+def test_all_zero_sparse_block(sim):
+    gc.check_all_zero_sparse_block(DEV)
+
+
+def test_unnormalised_dense_mapping(sim, golden_dir):
+    gc.check_unnormalised_dense_mapping(DEV, golden_dir)

@@ -61,3 +61,15 @@ def test_score_genes_refusals():
 
 def test_train_score_invariant():
     gc.check_train_score_invariant(DEV)
+
+
+def test_route_errors_are_the_same_in_project_genes_and_score_genes():
+    gc.check_route_errors(DEV)
+
+
+def test_all_zero_sparse_block():
+    gc.check_all_zero_sparse_block(DEV)
+
+
+def test_unnormalised_dense_mapping(golden_dir):
+    gc.check_unnormalised_dense_mapping(DEV, golden_dir)
