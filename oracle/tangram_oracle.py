@@ -319,7 +319,7 @@ class OracleMapper:
         if dM_extra is not None:
             dM = dM + dM_extra
         terms["total_loss"] = total
-        self.last = dict(P=P, Ghat=Ghat, dGhat=dGhat, dM=dM, r=r[:, 0])
+        self.last = dict(P=P, Ghat=Ghat, dGhat=dGhat, dM=dM, dP=dP, r=r[:, 0])
         return terms, dM
 
     def step(self, learning_rate=0.1):
@@ -418,7 +418,7 @@ class OracleMapperConstrained:
         dM = P * (dP - r)
         dF = df * fp * (1 - fp)
         terms["total_loss"] = total
-        self.last = dict(P=P, Ghat=Ghat, dGhat=dGhat, dM=dM, dF=dF, f=fp)
+        self.last = dict(P=P, Ghat=Ghat, dGhat=dGhat, dM=dM, dP=dP, r=r[:, 0], dF=dF, f=fp)
         return terms, dM, dF
 
     def step(self, learning_rate=0.1):

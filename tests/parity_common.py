@@ -276,28 +276,63 @@ def row_rel_err(got, ref, order=np.inf):
     return np.linalg.norm(got - ref, ord=order, axis=1) / np.where(scale > 0, scale, 1.0)
 
 
-def update_row_case(device, C, K, V, variant, precision, tile=0, expect_tile=128, n=3, seed=0):
-    """One problem of C > 32 cells on the GEMM path against the fp64 oracle, n epochs; returns the measured errors.
+# A trained state (tests/trained_state_cases.py): probabilities are compared relatively down to this floor, 2^-100 (a float32
+# normal number with 26 binades to spare); below it the library's value has to be below twice the floor
+P_FLOOR = 2.0 ** -100
+# ... and float32 has no relative precision below its smallest normal number, 2^-126: a gradient read from Adam's first moment
+# (1 - beta1) g is that coarse, and a probability below it may be flushed to 0 (v_exp_f32 does), which moves r_c = sum_v P dP by up to
+# V 2^-126 max|dP| and with it every g_cv = P (dP - r_c) of the row.  A row whose every term is that small -- a cell without counts
+# whose only spot with mass has density 0: dP = 0 at the peak, scale 3e-85 or 1e-34 in the fp64 oracle -- is held to this absolutely
+FLT_MIN_NORMAL = 2.0 ** -126
 
-    variant: "plain" (FULL off), "regularised" (lambda_r, lambda_l1, lambda_l2 on) or "constrained" (filter gate + lambda_r).
-    The regularisers are scaled to the plain gradient of the problem so that each term moves dM visibly without drowning the
-    rest.  Adam's eps is ROW_EPS_FRACTION[precision] of the largest first-step |dM|: with torch's 1e-8 the first step is lr * sign(g)
-    wherever |g| >> 1e-8, and the few elements whose gradient crosses zero within the round-off of the GEMM precision then
-    decide an element-wise comparison of P (measured: 5e-4 relative in bf16x3, 0.2 in bf16 at eps 1e-8).  The kernel's
-    arithmetic is the same for any eps."""
-    import ctypes as ct
-    from tangram_amd.engine import HipMapperEngine
-    from tangram_amd import _capi
+
+def grad_abs_floor(o):
+    """[C, 1] absolute allowance of the scaled gradient measure (above), from the oracle's last loss_and_grad."""
+    V = o.last["dP"].shape[1]
+    return FLT_MIN_NORMAL * (1.0 / (1.0 - 0.9) + V * np.abs(o.last["dP"]).max(axis=1, keepdims=True))
+
+
+def grad_scale_terms(o):
+    """|P| (|dP| + |r|) [C, V] of the oracle's last loss_and_grad: the size of the terms of dM = P (dP - r) before they cancel."""
+    L = o.last
+    return L["P"] * (np.abs(L["dP"]) + np.abs(L["r"])[:, None])
+
+
+def trained_P_errors(P, Po):
+    """(largest relative error over the elements with Po >= P_FLOOR, largest P over the others)"""
+    hi = Po >= P_FLOOR
+    rel = np.abs(P - Po)[hi] / Po[hi]
+    return float(rel.max()), float(P[~hi].max()) if (~hi).any() else 0.0
+
+
+def _as_f32_like(x, like):
+    import torch
+    return torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32), device=like.device)
+
+
+def _load_oracle_state(o, start):
+    """A checkpoint (m, v, t[, mF, vF]) into an oracle built on its logits; the library holds float32, so does the oracle's start."""
+    if "m" not in start:
+        return
+    f = lambda x: np.asarray(x, dtype=np.float32).astype(o.dt)      # noqa: E731
+    if hasattr(o, "mF"):
+        o.mM, o.vM, o.mF, o.vF = f(start["m"]), f(start["v"]), f(start["mF"]), f(start["vF"])
+    else:
+        o.m, o.v = f(start["m"]), f(start["v"])
+    o.t = int(start["t"])
+
+
+def update_row_problem(C, K, V, variant, seed):
+    """(data, lambdas, M0, F0) of update_row_case: make_synthetic(seed), the reference's initial draw of seed + 1, and for the
+    variants but "plain" each regulariser at a fraction of the typical |dM| of the plain problem at that draw."""
     from oracle import tangram_oracle as orc
-    lr = 0.1
-    kind = update_instantiation(C, V, precision, variant)
     data = orc.make_synthetic(C, K, V, seed=seed)
     lam = dict(lambda_g1=1.0, lambda_d=1.0, lambda_g2=0.5)
     if variant == "constrained":
         M0, F0 = orc.reference_init_MF_constrained(C, V, seed + 1)
     else:
         M0, F0 = orc.reference_init_M(C, V, seed + 1), None
-    if variant != "plain":                # each regulariser at a fraction of the typical |dM| of the plain problem
+    if variant != "plain":
         _, g0 = orc.OracleMapper(data["S"], data["G"], d=data["d"], M0=M0, dtype=np.float64, **lam).loss_and_grad()
         P0 = orc.softmax_rows(M0.astype(np.float64))
         logP = np.log(P0)
@@ -309,24 +344,130 @@ def update_row_case(device, C, K, V, variant, precision, tile=0, expect_tile=128
             lam["lambda_l2"] = float(np.float32(0.1 * gmed))
     if variant == "constrained":
         lam.update(lambda_count=1.0, lambda_f_reg=1.0)
-        tc = 0.4 * C
-        o = orc.OracleMapperConstrained(data["S"], data["G"], data["d"], M0=M0, F0=F0, target_count=tc, dtype=np.float64, **lam)
-        kw = dict(F0=F0, mode="constrained", target_count=tc)
-    else:
-        o = orc.OracleMapper(data["S"], data["G"], d=data["d"], M0=M0, dtype=np.float64, **lam)
-        kw = {}
-    dM = o.loss_and_grad()[1]
-    eps = float(np.float32(ROW_EPS_FRACTION[precision] * np.abs(dM).max()))
+    return data, lam, M0, F0
+
+
+def update_row_oracle(data, lam, M0, F0, variant, dtype=np.float64):
+    """The oracle of update_row_case at the logits M0 (and filter logits F0): target count 0.4 C in constrained mode."""
+    from oracle import tangram_oracle as orc
+    if variant == "constrained":
+        return orc.OracleMapperConstrained(data["S"], data["G"], data["d"], M0=M0, F0=F0, target_count=0.4 * M0.shape[0], dtype=dtype, **lam)
+    return orc.OracleMapper(data["S"], data["G"], d=data["d"], M0=M0, dtype=dtype, **lam)
+
+
+def _conditioning_guard(o64, data, lam, variant, M0, F0, start, eps, lr, n, dM, sc, floor, hist_o, cols, tol, ltol):
+    """The oracle in float32 on the same case, measured like the library, against a third of each bound -- on the elements and
+    columns where the float32 run is finite (lambda_r with an underflowed probability is 0 * log 0 = NaN there, as in the
+    reference).  A condition on the inputs, evaluated on the checker alone."""
+    from oracle import tangram_oracle as orc
+    o = update_row_oracle(data, lam, M0, F0, variant, dtype=np.float32)
+    _load_oracle_state(o, start)
+    hist = []
+    with np.errstate(all="ignore"):
+        for i in range(n):
+            terms, g = _oracle_adam_step(o, np.float32(eps), lr)
+            hist.append(terms)
+            if i == 0:
+                g32 = g.astype(np.float64)
+        P32 = orc.softmax_rows(o.M).astype(np.float64)
+    guard = {}
+    err = np.where(np.isfinite(g32), np.maximum(np.abs(g32 - dM) - floor, 0.0), 0.0).max(axis=1) / sc.max(axis=1)
+    guard["grad"] = float(err.max())
+    Po = orc.softmax_rows(o64.M)
+    okP = np.isfinite(P32) & (Po >= P_FLOOR)
+    guard["P"] = float((np.abs(P32 - Po)[okP] / Po[okP]).max()) if okP.any() else 0.0
+    guard["hist"] = 0.0
+    for _, k in cols:
+        ref = np.array([float(x) for x in hist_o[k]])
+        got = np.array([float(t[k]) for t in hist], dtype=np.float64)
+        fin = np.isfinite(got)
+        if fin.any():
+            guard["hist"] = max(guard["hist"], float(np.abs(got - ref)[fin].max() / max(1.0, float(np.abs(ref).max()))))
+    assert guard["grad"] <= tol["grad"] / 3, f"inputs: the oracle's float32 gradient is {guard['grad']:.2e} off (> {tol['grad'] / 3:.1e})"
+    assert guard["P"] <= tol["P"] / 3, f"inputs: the oracle's float32 mapping is {guard['P']:.2e} off (> {tol['P'] / 3:.1e})"
+    assert guard["hist"] <= ltol / 3, f"inputs: the oracle's float32 history is {guard['hist']:.2e} off (> {ltol / 3:.1e})"
+    return guard
+
+
+def _readouts_at_state(e, o, data, variant, P32, precision, seed):
+    """The read-outs of a handle at its stepped state against fp64 from the oracle's logits: result_topk(8) bit-equal to result(),
+    project() and project_genes of 300 genes within relFro TOL[precision]["ghat"]."""
+    from oracle import tangram_oracle as orc
+    from tests.topk_cases import assert_topk_equals_dense
+    assert_topk_equals_dense(e.result_topk(8), P32, 8, "top-k at the stepped state")
+    Po = orc.softmax_rows(o.M)
+    S = data["S"].astype(np.float64)
+    ref = Po.T @ (S * (1.0 / (1.0 + np.exp(-o.F)))[:, None]) if variant == "constrained" else Po.T @ S
+    got = e.project().cpu().numpy().astype(np.float64)
+    bound = TOL[precision]["ghat"]
+    rel = float(np.linalg.norm(got - ref) / np.linalg.norm(ref))
+    assert np.isfinite(got).all() and rel <= bound, f"project(): relFro {rel:.3e} > {bound:.0e}"
+    S_all = (np.random.default_rng(seed).poisson(0.7, size=(e.C, 300))).astype(np.float32)
+    got = e.project_genes(S_all).cpu().numpy().astype(np.float64)
+    ref = Po.T @ S_all.astype(np.float64)
+    rel = float(np.linalg.norm(got - ref) / np.linalg.norm(ref))
+    assert np.isfinite(got).all() and rel <= bound, f"project_genes of 300 genes: relFro {rel:.3e} > {bound:.0e}"
+
+
+def update_row_case(device, C, K, V, variant, precision, tile=0, expect_tile=128, n=3, seed=0, start=None, grad_scale=None,
+                    smallc=False, readouts=False):
+    """One problem of C > 32 cells on the GEMM path against the fp64 oracle, n epochs; returns the measured errors.
+
+    variant: "plain" (FULL off), "regularised" (lambda_r, lambda_l1, lambda_l2 on) or "constrained" (filter gate + lambda_r).
+    The regularisers are scaled to the plain gradient of the problem so that each term moves dM visibly without drowning the
+    rest.  Adam's eps is ROW_EPS_FRACTION[precision] of the largest first-step |dM|: with torch's 1e-8 the first step is lr * sign(g)
+    wherever |g| >> 1e-8, and the few elements whose gradient crosses zero within the round-off of the GEMM precision then
+    decide an element-wise comparison of P (measured: 5e-4 relative in bf16x3, 0.2 in bf16 at eps 1e-8).  The kernel's
+    arithmetic is the same for any eps.
+
+    start: the state the run begins from instead of the reference's N(0, 1) draw (tests/trained_state_cases.py) -- a dict with
+    "M" [C, V] float32, "F" [C] for constrained, and for a checkpoint "m", "v", "t" (and "mF", "vF"), copied into the handle
+    through logits() / filter_state() / set_step; "eps" overrides Adam's eps.  The regularisers keep the scale they have from the
+    N(0, 1) draw of the same seed.  With a start the case asserts more (the trained-state list of _trained_checks) and the
+    conditioning guard: the oracle's own float32 run stays within a third of every bound.
+    grad_scale="terms": the first-step gradient is held per row against max_v P_cv (|dP_cv| + |r_c|) of the fp64 oracle, which
+    does not cancel on a saturated row, instead of max_v |dM_cv|; every precision in the max norm.
+    smallc: a problem of at most 32 cells on the clusters-mode kernels (tg_sc_forward / tg_sc_backward; bounds: the fp32 row).
+    readouts: result_topk(8), project() and project_genes of 300 genes at the stepped state against fp64."""
+    import ctypes as ct
+    from tangram_amd.engine import HipMapperEngine
+    from tangram_amd import _capi
+    from oracle import tangram_oracle as orc
+    lr = 0.1
+    kind = None if smallc else update_instantiation(C, V, precision, variant)
+    start = dict(start or {})
+    data, lam, M0, F0 = update_row_problem(C, K, V, variant, seed)
+    if "M" in start:
+        M0, F0 = start["M"], start.get("F")
+    o = update_row_oracle(data, lam, M0, F0, variant)
+    kw = dict(F0=F0, mode="constrained", target_count=0.4 * C) if variant == "constrained" else {}
+    _load_oracle_state(o, start)
+    terms0, dM = o.loss_and_grad()[:2]
+    eps = float(start.get("eps") or np.float32(ROW_EPS_FRACTION[precision] * np.abs(dM).max()))
+    if start:                             # the inputs: every term the case compares is finite in the fp64 oracle before the library is called
+        on = [k for k in terms0 if not (k == "entropy_reg" and "lambda_r" not in lam)]
+        assert all(np.isfinite(float(terms0[k])) for k in on) and np.isfinite(dM).all(), f"inputs: fp64 terms {terms0}"
     e = HipMapperEngine(data["S"], data["G"], M0, d=data["d"], device=device, precision=precision, lambdas=lam, tile_size=tile,
                         eps=eps, **kw)
-    tol = ROW_TOL[precision]
+    tol = ROW_TOL["fp32" if smallc else precision]
+    ltol = TOL["fp32" if smallc else precision]["loss"]
     out = dict(kind=kind, eps=eps)
     # ---- schedule: the GEMM path (not the clusters-mode kernels), the tile, one cell band
     geo = (ct.c_int * 8)()
     assert e._lib.tg_debug_layout(ct.byref(e.cfg), geo) == 0
-    assert (geo[7], geo[0], geo[6]) == (0, expect_tile, 1), f"smallc / tile / bands = {geo[7]}, {geo[0]}, {geo[6]}"
+    assert (geo[7], geo[0], geo[6]) == (int(smallc), expect_tile, 1), f"smallc / tile / bands = {geo[7]}, {geo[0]}, {geo[6]}"
     M, m1, m2, _ = e.logits()
     pitch = M.shape[1]
+    if "m" in start:                      # a checkpoint: moments and step counter into the fresh handle (the logits came with create)
+        m1[:, :V].copy_(_as_f32_like(start["m"], m1))
+        m2[:, :V].copy_(_as_f32_like(start["v"], m2))
+        if variant == "constrained":
+            fs = e.filter_state()
+            fs[1, :C].copy_(_as_f32_like(start["mF"], fs))
+            fs[2, :C].copy_(_as_f32_like(start["vF"], fs))
+        e.set_step(int(start["t"]))
+        assert e.logits()[3] == int(start["t"]) == o.t
+    m1_before = m1[:, :V].cpu().numpy().astype(np.float64)
     pad0 = [x[:, V:].cpu().numpy().copy() for x in (M, m1, m2)]
     if variant == "constrained":
         fs = e.filter_state()
@@ -336,7 +477,10 @@ def update_row_case(device, C, K, V, variant, precision, tile=0, expect_tile=128
     e.step(1, lr, hist, 0)
     names = [k for k, _, _ in e.profile_read()]
     e.profile(False)
-    if kind[0] == "tg_adam_rowpass":
+    if smallc:
+        assert "tg_sc_forward" in names and "tg_sc_backward" in names and "tg_fwd_kernel" not in names, names
+    elif kind[0] == "tg_adam_rowpass":
+        assert "tg_fwd_kernel" in names and "tg_sc_forward" not in names, names
         assert "tg_adam_rowpass" in names and "tg_adam_update" not in names and "tg_rowsum_parts" not in names, names
     else:
         assert "tg_rowsum_parts" in names and "tg_adam_update" in names and "tg_adam_rowpass" not in names, names
@@ -344,11 +488,22 @@ def update_row_case(device, C, K, V, variant, precision, tile=0, expect_tile=128
     terms, dM1 = _oracle_adam_step(o, eps, lr)
     assert np.array_equal(dM1, dM)
     hist_o = {k: [terms.get(k, np.nan)] for k in terms}
-    g = m1[:, :V].cpu().numpy().astype(np.float64) / (1.0 - 0.9)
-    err_row = row_rel_err(g, dM, ROW_GRAD_NORM[precision])
-    # the last four columns of every row on their own (the quad that straddles V when V % 4 != 0), against their own largest |dM|
     q0 = max(0, V - 4)
-    err_quad = np.abs(g[:, q0:] - dM[:, q0:]).max(axis=1) / np.abs(dM[:, q0:]).max()
+    if "m" in start:                      # exp_avg = beta1 * exp_avg + (1 - beta1) * g
+        g = (m1[:, :V].cpu().numpy().astype(np.float64) - 0.9 * m1_before) / 0.1
+    else:
+        g = m1[:, :V].cpu().numpy().astype(np.float64) / (1.0 - 0.9)
+    if grad_scale == "terms":
+        sc, floor = grad_scale_terms(o), grad_abs_floor(o)
+        dg = np.maximum(np.abs(g - dM) - floor, 0.0)
+        err_row = dg.max(axis=1) / sc.max(axis=1)
+        err_quad = dg[:, q0:].max(axis=1) / sc[:, q0:].max()
+    else:
+        assert grad_scale is None, grad_scale
+        sc, floor = np.abs(dM), 0.0
+        err_row = row_rel_err(g, dM, ROW_GRAD_NORM[precision])
+        # the last four columns of every row on their own (the quad that straddles V when V % 4 != 0), against their own largest |dM|
+        err_quad = np.abs(g[:, q0:] - dM[:, q0:]).max(axis=1) / np.abs(dM[:, q0:]).max()
     out["grad"] = float(err_row.max())
     out["grad_quad"] = float(err_quad.max())
     assert out["grad"] <= tol["grad"], f"first-step gradient: row {int(err_row.argmax())}, {out['grad']:.3e} > {tol['grad']:.0e}"
@@ -368,17 +523,30 @@ def update_row_case(device, C, K, V, variant, precision, tile=0, expect_tile=128
         cols += [(_capi.H_COUNT, "count_reg"), (_capi.H_FREG, "lambda_f_reg")]
     for col, k in cols:
         ref = np.array([float(x) for x in hist_o[k]])
+        if start:
+            assert np.isfinite(ref).all(), f"inputs: {k} of the fp64 oracle {ref}"
+            assert np.isfinite(h[:, col]).all(), f"{k}: {h[:, col]} where the fp64 oracle has {ref}"
         err = float(np.abs(h[:, col] - ref).max())
-        assert err <= TOL[precision]["loss"] * max(1.0, float(np.abs(ref).max())), f"{k}: max per-epoch |delta| {err:.3e}"
+        out["hist"] = max(out.get("hist", 0.0), err / max(1.0, float(np.abs(ref).max())))
+        assert err <= ltol * max(1.0, float(np.abs(ref).max())), f"{k}: max per-epoch |delta| {err:.3e}"
     if variant == "constrained":
         P, Fg = e.result(with_filter=True)
     else:
         P = e.result()
-    P = P.cpu().numpy().astype(np.float64)
+    P32 = P.cpu().numpy()
+    P = P32.astype(np.float64)
     Po = orc.softmax_rows(o.M)
-    out["P"] = float((np.abs(P - Po) / Po).max())
+    if start:
+        out["P"], out["P_low"] = trained_P_errors(P, Po)
+        assert np.isfinite(P).all()
+        assert out["P_low"] <= P_FLOOR * 2, f"an element below the floor holds {out['P_low']:.3e}"
+        assert float(np.abs(P32.sum(axis=1, dtype=np.float64) - 1.0).max()) <= 1e-6, "rows of result() do not sum to 1"
+        for c in start.get("zero_rows", ()):
+            assert (np.delete(P32[c], int(np.argmax(start["M"][c]))) == 0).all() and P32[c].max() == 1.0, f"row {c}: exact zeros expected off the peak"
+    else:
+        out["P"] = float((np.abs(P - Po) / Po).max())
     assert out["P"] <= tol["P"], f"max|P - Po| / Po = {out['P']:.3e} > {tol['P']:.0e}"
-    bc2 = np.sqrt(1.0 - 0.999 ** n)
+    bc2 = np.sqrt(1.0 - 0.999 ** o.t)
 
     def den_err(v, vo):
         den, deno = np.sqrt(v) / bc2 + eps, np.sqrt(vo) / bc2 + eps
@@ -391,6 +559,7 @@ def update_row_case(device, C, K, V, variant, precision, tile=0, expect_tile=128
         out["F"] = float((np.abs(fs[0, :C] - o.F) / np.maximum(1.0, np.abs(o.F))).max())
         out["F_den"] = den_err(fs[2, :C], o.vF)
         fo = 1.0 / (1.0 + np.exp(-o.F))
+        assert np.isfinite(fs).all()
         assert float(np.abs(Fg.cpu().numpy() - fo).max()) <= tol["P"]
         assert out["F"] <= tol["P"], f"filter logits: {out['F']:.3e}"
         assert float(np.abs(fs[1, :C] - o.mF).max()) <= tol["grad"] * float(np.abs(o.mF).max()), "filter first moment"
@@ -400,6 +569,11 @@ def update_row_case(device, C, K, V, variant, precision, tile=0, expect_tile=128
     for name, x, x0 in zip(("M", "exp_avg", "exp_avg_sq"), (M, m1, m2), pad0):
         assert x.shape[1] == pitch
         assert np.array_equal(x[:, V:].cpu().numpy(), x0), f"padding of {name} changed"
+    if start:
+        assert np.isfinite(M[:, :V].cpu().numpy()).all() and np.isfinite(m2[:, :V].cpu().numpy()).all(), "a logit or a moment is not finite"
+        out["guard"] = _conditioning_guard(o, data, lam, variant, M0, F0, start, eps, lr, n, dM, sc, floor, hist_o, cols, tol, ltol)
+    if readouts:
+        _readouts_at_state(e, o, data, variant, P32, precision if not smallc else "fp32", seed)
     e.release()
     return out
 
