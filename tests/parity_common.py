@@ -322,18 +322,27 @@ def _load_oracle_state(o, start):
     o.t = int(start["t"])
 
 
-def update_row_problem(C, K, V, variant, seed):
+def update_row_problem(C, K, V, variant, seed, lambda_g2=0.5, d_source=False, density=True, lambda_d=1.0):
     """(data, lambdas, M0, F0) of update_row_case: make_synthetic(seed), the reference's initial draw of seed + 1, and for the
-    variants but "plain" each regulariser at a fraction of the typical |dM| of the plain problem at that draw."""
+    variants but "plain" each regulariser at a fraction of the typical |dM| of the plain problem at that draw.
+    lambda_g2 = 0 turns the per-spot cosine term off; d_source: data["d_source"] is a strictly positive [C] float32 vector that sums
+    to 1, drawn from `seed` (Mapper only: the constrained mapper takes none); density off: lambda_d = 0 and data["d"] is None."""
     from oracle import tangram_oracle as orc
-    data = orc.make_synthetic(C, K, V, seed=seed)
-    lam = dict(lambda_g1=1.0, lambda_d=1.0, lambda_g2=0.5)
+    data = dict(orc.make_synthetic(C, K, V, seed=seed), d_source=None)
+    lam = dict(lambda_g1=1.0, lambda_d=float(lambda_d), lambda_g2=lambda_g2)
+    if not density:
+        assert not d_source, "d_source requires d"
+        lam["lambda_d"], data["d"] = 0.0, None
+    if d_source:
+        assert variant != "constrained", "the constrained mapper takes no d_source"
+        w = np.random.default_rng(seed).uniform(0.5, 1.5, size=C)
+        data["d_source"] = (w / w.sum()).astype(np.float32)
     if variant == "constrained":
         M0, F0 = orc.reference_init_MF_constrained(C, V, seed + 1)
     else:
         M0, F0 = orc.reference_init_M(C, V, seed + 1), None
     if variant != "plain":
-        _, g0 = orc.OracleMapper(data["S"], data["G"], d=data["d"], M0=M0, dtype=np.float64, **lam).loss_and_grad()
+        _, g0 = orc.OracleMapper(data["S"], data["G"], d=data["d"], d_source=data["d_source"], M0=M0, dtype=np.float64, **lam).loss_and_grad()
         P0 = orc.softmax_rows(M0.astype(np.float64))
         logP = np.log(P0)
         ent = np.median(np.abs(P0 * (logP - (P0 * logP).sum(axis=1, keepdims=True))))
@@ -352,7 +361,7 @@ def update_row_oracle(data, lam, M0, F0, variant, dtype=np.float64):
     from oracle import tangram_oracle as orc
     if variant == "constrained":
         return orc.OracleMapperConstrained(data["S"], data["G"], data["d"], M0=M0, F0=F0, target_count=0.4 * M0.shape[0], dtype=dtype, **lam)
-    return orc.OracleMapper(data["S"], data["G"], d=data["d"], M0=M0, dtype=dtype, **lam)
+    return orc.OracleMapper(data["S"], data["G"], d=data["d"], d_source=data.get("d_source"), M0=M0, dtype=dtype, **lam)
 
 
 def _conditioning_guard(o64, data, lam, variant, M0, F0, start, eps, lr, n, dM, sc, floor, hist_o, cols, tol, ltol):
@@ -410,7 +419,7 @@ def _readouts_at_state(e, o, data, variant, P32, precision, seed):
 
 
 def update_row_case(device, C, K, V, variant, precision, tile=0, expect_tile=128, n=3, seed=0, start=None, grad_scale=None,
-                    smallc=False, readouts=False):
+                    smallc=False, readouts=False, lambda_g2=0.5, d_source=False, density=True, lambda_d=1.0):
     """One problem of C > 32 cells on the GEMM path against the fp64 oracle, n epochs; returns the measured errors.
 
     variant: "plain" (FULL off), "regularised" (lambda_r, lambda_l1, lambda_l2 on) or "constrained" (filter gate + lambda_r).
@@ -428,7 +437,9 @@ def update_row_case(device, C, K, V, variant, precision, tile=0, expect_tile=128
     grad_scale="terms": the first-step gradient is held per row against max_v P_cv (|dP_cv| + |r_c|) of the fp64 oracle, which
     does not cancel on a saturated row, instead of max_v |dM_cv|; every precision in the max norm.
     smallc: a problem of at most 32 cells on the clusters-mode kernels (tg_sc_forward / tg_sc_backward; bounds: the fp32 row).
-    readouts: result_topk(8), project() and project_genes of 300 genes at the stepped state against fp64."""
+    readouts: result_topk(8), project() and project_genes of 300 genes at the stepped state against fp64.
+    lambda_g2, d_source, density, lambda_d: update_row_problem; a term that is turned off (vg_reg at lambda_g2 = 0, kl_reg without a
+    density) is NaN in the history, as in the reference, and its column is not compared."""
     import ctypes as ct
     from tangram_amd.engine import HipMapperEngine
     from tangram_amd import _capi
@@ -436,7 +447,7 @@ def update_row_case(device, C, K, V, variant, precision, tile=0, expect_tile=128
     lr = 0.1
     kind = None if smallc else update_instantiation(C, V, precision, variant)
     start = dict(start or {})
-    data, lam, M0, F0 = update_row_problem(C, K, V, variant, seed)
+    data, lam, M0, F0 = update_row_problem(C, K, V, variant, seed, lambda_g2=lambda_g2, d_source=d_source, density=density, lambda_d=lambda_d)
     if "M" in start:
         M0, F0 = start["M"], start.get("F")
     o = update_row_oracle(data, lam, M0, F0, variant)
@@ -447,8 +458,8 @@ def update_row_case(device, C, K, V, variant, precision, tile=0, expect_tile=128
     if start:                             # the inputs: every term the case compares is finite in the fp64 oracle before the library is called
         on = [k for k in terms0 if not (k == "entropy_reg" and "lambda_r" not in lam)]
         assert all(np.isfinite(float(terms0[k])) for k in on) and np.isfinite(dM).all(), f"inputs: fp64 terms {terms0}"
-    e = HipMapperEngine(data["S"], data["G"], M0, d=data["d"], device=device, precision=precision, lambdas=lam, tile_size=tile,
-                        eps=eps, **kw)
+    e = HipMapperEngine(data["S"], data["G"], M0, d=data["d"], d_source=data["d_source"], device=device, precision=precision, lambdas=lam,
+                        tile_size=tile, eps=eps, **kw)
     tol = ROW_TOL["fp32" if smallc else precision]
     ltol = TOL["fp32" if smallc else precision]["loss"]
     out = dict(kind=kind, eps=eps)
@@ -516,7 +527,11 @@ def update_row_case(device, C, K, V, variant, precision, tile=0, expect_tile=128
             hist_o[k].append(terms.get(k, np.nan))
     e.step(n - 1, lr, hist, 1)
     h = hist.cpu().numpy().astype(np.float64)
-    cols = [(_capi.H_TOTAL, "total_loss"), (_capi.H_MAIN, "main_loss"), (_capi.H_VG, "vg_reg"), (_capi.H_KL, "kl_reg")]
+    cols = [(_capi.H_TOTAL, "total_loss"), (_capi.H_MAIN, "main_loss")]
+    if lam["lambda_g2"] != 0:
+        cols.append((_capi.H_VG, "vg_reg"))
+    if data["d"] is not None:
+        cols.append((_capi.H_KL, "kl_reg"))
     if "lambda_r" in lam:
         cols.append((_capi.H_ENTROPY, "entropy_reg"))
     if variant == "constrained":
