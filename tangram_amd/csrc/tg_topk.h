@@ -206,6 +206,9 @@ TG_DEV unsigned tg_topk_okey(float f) {
 TG_DEV float tg_topk_okey_inv(unsigned o) { return __builtin_bit_cast(float, (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
 
 // One workgroup per row.  The indices of a row's real entries must be pairwise different (they are spots of different shards).
+// An entry here is {okey(value), ~index << 1 | sign bit of a zero}: -0.0 takes the key of +0.0 -- the two are equal as floats, so the
+// lower spot index decides between them like between any equal values -- and its sign bit travels in the bit that ~index leaves free
+// (an index is below 2^31: the top bit of ~index is always set and need not be stored); the indices differ, so it never decides an order.
 TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_topk_merge_rows(const float* val_in, const int* idx_in, int n_in, long long ld_in, int k,
                                                         float* val_out, int* idx_out) {
     TG_LDS_DECL;
@@ -219,7 +222,9 @@ TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_topk_merge_rows(const float* val_in, con
         for (int i = t; i < n; i += 256) {
             const float v = val_in[row * ld_in + j0 + i];
             const int ix = idx_in[row * ld_in + j0 + i];
-            list[ncarry + i] = ix < 0 ? 0ull : (((tg_u64)tg_topk_okey(v) << 32) | (tg_u64)(~(unsigned)ix));     // a pad: behind everything
+            const bool negzero = __builtin_bit_cast(unsigned, v) == 0x80000000u;
+            list[ncarry + i] = ix < 0 ? 0ull                                                                    // a pad: behind everything
+                                      : (((tg_u64)tg_topk_okey(negzero ? 0.f : v) << 32) | (tg_u64)((~(unsigned)ix << 1) | (negzero ? 1u : 0u)));
         }
         __syncthreads();
         tg_topk_rank_keep(list, ncarry + n, k, keep);
@@ -228,7 +233,7 @@ TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_topk_merge_rows(const float* val_in, con
     for (int r = t; r < k; r += 256) {
         const tg_u64 e = list[r];
         const bool real = e != 0ull;
-        val_out[row * k + r] = real ? tg_topk_okey_inv((unsigned)(e >> 32)) : 0.f;
-        idx_out[row * k + r] = real ? (int)~(unsigned)e : -1;
+        val_out[row * k + r] = real ? (((unsigned)e & 1u) ? -0.f : tg_topk_okey_inv((unsigned)(e >> 32))) : 0.f;
+        idx_out[row * k + r] = real ? (int)~(((unsigned)e >> 1) | 0x80000000u) : -1;
     }
 }

@@ -144,7 +144,10 @@ def test_emulated_constrained_handle_refuses_validation(sim):
 
 
 # (world, K, rank whose block holds no spot of gene 0): 1 010 spots are ragged on 2 and on 3 shards; 300 genes are two voxstat parts
-SHARDS = [(2, 48, None), (3, 300, None), (3, 48, 1)]
+SHARDS = [(2, 48, None), (3, 300, None), (3, 48, 1),
+          # nine and sixteen shards: the second trip of the eight-wide per-rank loops (tests/many_rank_cases.py); the rank without a
+          # spot of gene 0 is one of the second trip
+          (9, 300, None), (16, 300, 11)]
 
 
 @pytest.mark.parametrize("world,K,empty", SHARDS, ids=[f"world{w}-genes{K}" + ("-gene-empty-on-a-shard" if e is not None else "") for w, K, e in SHARDS])

@@ -25,17 +25,27 @@ KERNEL_CASES = [(40, 5, V, "bf16x3") for V in (1, 2, 63, 64, 65, 255, 256, 257, 
                [(3, 5, V, "bf16x3") for V in (CHUNK - 1, CHUNK, CHUNK + 1, 2 * CHUNK + 3)] + \
                [(40, 5, 257, "fp32"), (40, 5, 257, "bf16")]
 TIE_LAYOUTS = ("one-chunk", "across-the-chunk-boundary")
-MERGE_CASES = [(n_in, k) for k in (1, 5, 64) for n_in in sorted({k, 2 * k, 3 * k + 1, 512})]
-SHARD_CASES = [(world, V, k) for world in (2, 3) for V, k in ((100, 7), (10, 5), (131, 64))]
+MERGE_CHUNK = 512                 # TG_MERGE_CHUNK of tg_topk.h: entries tg_topk_merge_rows ranks at a time, k survivors carried on
+# past one chunk (the carry of tg_topk_merge_rows): one entry, k - 1, k and k + 1 entries (k = 64) into the second chunk -- 576 is nine
+# shards of 64 --, one short of two chunks, two chunks (sixteen shards of 64), one entry into the third and into the fourth
+MERGE_CARRY_N = (513, 575, 576, 577, 1023, 1024, 1025, 1537)
+MERGE_CASES = [(n_in, k) for k in (1, 5, 64) for n_in in sorted({k, 2 * k, 3 * k + 1, 512}) + list(MERGE_CARRY_N)]
+# worlds 9 and 16: the lists of a row are 9 k and 16 k long, 576 and 1 024 at k = 64 (131 spots: every shard narrower than k)
+SHARD_CASES = [(world, V, k) for world in (2, 3) for V, k in ((100, 7), (10, 5), (131, 64))] + \
+              [(world, V, k) for world in (9, 16) for V, k in ((131, 64), (1010, 64), (100, 7))]
 
 
 def check_case_tables():
     assert {V for _, _, V, _ in KERNEL_CASES} >= {1, 2, 63, 64, 65, 255, 256, 257, 1023, 1025, CHUNK - 1, CHUNK, CHUNK + 1, 2 * CHUNK + 3}
     assert {C for C, _, _, _ in KERNEL_CASES} == {3, 18, 40} and {p for *_, p in KERNEL_CASES} == {"bf16x3", "fp32", "bf16"}
     assert all(C * V * 4 < (1 << 20) for C, _, V, _ in KERNEL_CASES if V >= CHUNK - 1)
-    assert {n for n, _ in MERGE_CASES} >= {1, 2, 4, 5, 10, 16, 64, 128, 193, 512} and {k for _, k in MERGE_CASES} == {1, 5, 64}
-    assert {(w, V) for w, V, _ in SHARD_CASES} == {(w, V) for w in (2, 3) for V in (100, 10, 131)}
+    assert {n for n, _ in MERGE_CASES} >= {1, 2, 4, 5, 10, 16, 64, 128, 193, 512} | set(MERGE_CARRY_N) and {k for _, k in MERGE_CASES} == {1, 5, 64}
+    assert set(MERGE_CARRY_N) == {513, 575, 576, 577, 1023, 1024, 1025, 1537} and MERGE_CHUNK == 512
+    assert all((n, k) in MERGE_CASES for n in MERGE_CARRY_N for k in (1, 5, 64))
+    assert {(w, V) for w, V, _ in SHARD_CASES} == {(w, V) for w in (2, 3) for V in (100, 10, 131)} | {(w, V) for w in (9, 16) for V in (131, 1010, 100)}
     assert all(-(-10 // 3) < k for w, V, k in SHARD_CASES if (w, V) == (3, 10))             # every shard narrower than k
+    assert {(w, w * k) for w, V, k in SHARD_CASES if V == 131 and w > 8} == {(9, 576), (16, 1024)}      # n_in of the merge: past one chunk
+    assert all(-(-131 // w) < k for w, V, k in SHARD_CASES if V == 131 and w > 8)
 
 
 def check_limits():
@@ -175,15 +185,108 @@ def check_merge(device, n_in, k):
     pad[7, : n_in - min(n_in, max(k - 1, 1))] = True                          # fewer than k real entries where the list allows
     idx[pad] = -1
     val[pad] = 9.0
+    ri = _merge_against_reference(dev, val, idx, n_in, k, "")
+    assert (ri[5] == -1).all() and (ri[6] >= 0).sum() == min(k, n_in)
+    if n_in > MERGE_CHUNK:
+        val, idx, expect = merge_carry_rows(n_in, k)
+        ri = _merge_against_reference(dev, val, idx, n_in, k, " (carry rows)")
+        for row, want in expect.items():
+            got = ri[CARRY_ROWS[row]].tolist()[:len(want)]            # (fewer than k placed entries: they lead, the background follows)
+            assert got == want, (row, n_in, k, got, want)
+
+
+def _merge_against_reference(dev, val, idx, n_in, k, what):
+    """tg_topk_merge on the lists val / idx [n_rows, ld >= n_in] against merge_reference, indices equal and values bit for bit;
+    returns the reference's indices."""
+    n_rows, ld = val.shape
     tv, ti = torch.as_tensor(val, device=dev), torch.as_tensor(idx, device=dev)
     out_v = torch.full((n_rows, k), 7.0, dtype=torch.float32, device=dev)
     out_i = torch.full((n_rows, k), 7, dtype=torch.int32, device=dev)
     stream = ct.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
     _capi.check(_capi.lib().tg_topk_merge(tv.data_ptr(), ti.data_ptr(), n_rows, n_in, ld, k, out_v.data_ptr(), out_i.data_ptr(), stream))
     rv, ri = merge_reference(val[:, :n_in], idx[:, :n_in], k)
-    np.testing.assert_array_equal(_np(out_i), ri, err_msg=f"merge n_in={n_in} k={k}: indices")
-    np.testing.assert_array_equal(_np(out_v).view(np.uint32), rv.view(np.uint32), err_msg=f"merge n_in={n_in} k={k}: values")
-    assert (ri[5] == -1).all() and (ri[6] >= 0).sum() == min(k, n_in)
+    np.testing.assert_array_equal(_np(out_i), ri, err_msg=f"merge n_in={n_in} k={k}{what}: indices")
+    np.testing.assert_array_equal(_np(out_v).view(np.uint32), rv.view(np.uint32), err_msg=f"merge n_in={n_in} k={k}{what}: values")
+    return ri
+
+
+# The rows of merge_carry_rows: lists longer than one chunk of tg_topk_merge_rows, built so that the k entries carried from chunk to
+# chunk decide the result.
+CARRY_ROWS = dict(winners_last=0, winners_first=1, winners_first_scattered=2, tie_across_512=3, pads_interleaved=4, first_chunk_all_pads=5,
+                  later_chunk_all_pads=6, fewer_than_k=7, none_real=8, signs_zeros_denormals=9, zeros_across_512=10)
+
+
+def merge_carry_rows(n_in, k):
+    """(val [11, n_in + 3] float32, idx int32, {row name: expected indices}) for n_in > MERGE_CHUNK.  Real entries of a row carry
+    pairwise different spot indices in an order unrelated to their position; the background lies in [-3, -2); a pad has index -1 and
+    the value 9 (above every real one: it must lose on its index alone).
+
+    winners_last             the k largest values at the last k positions (the last chunk and, where it is shorter than k, the end of
+                             the one before): nothing of the first chunk survives
+    winners_first(_scattered) the k largest at positions 0 .. k - 1, and scattered over the first chunk: the result is the carry alone
+    tie_across_512           one value at positions 512 - k .. 512 + k - 1; the positions from 512 on hold the lower spot indices, so
+                             the winners arrive in the later chunk and displace equal carried entries
+    pads_interleaved         every second entry a pad;  first_chunk_all_pads / later_chunk_all_pads: positions 0 .. 511 / 512 .. 1023
+                             (or to the end) are pads -- a chunk that adds nothing to the carry, a carry of pads only
+    fewer_than_k             k - 1 real entries (none for k = 1), half of them behind position 512: the row ends in (0, -1)
+    none_real                pads only
+    signs_zeros_denormals    the candidates are +-1e-40 and +-1.4e-45 (denormals), +0.0, -0.0, -1.0 and 2^-126, on both sides of 512; the
+                             rest of the row is below -2, so every k takes them in float order
+    zeros_across_512         +0.0 and -0.0 are the largest values, they compare equal as floats: the lower spot index wins whatever its
+                             sign bit and its chunk, and the sign bit comes out as it went in"""
+    assert n_in > MERGE_CHUNK and 1 <= k <= 64
+    rng = np.random.default_rng(7000 * n_in + k)
+    n_rows, ld, E = len(CARRY_ROWS), n_in + 3, MERGE_CHUNK
+    val = -2.0 - rng.random((n_rows, ld), dtype=np.float32)
+    idx = np.stack([rng.permutation(4 * n_in + 7)[:ld] for _ in range(n_rows)]).astype(np.int32)
+    top = (5.0 + np.arange(k, dtype=np.float32))[rng.permutation(k)]
+    expect = {}
+
+    def put(row, pos, values):
+        r = CARRY_ROWS[row]
+        val[r, pos] = values
+        order = np.lexsort((idx[r, pos], -np.asarray(values, dtype=np.float64)))[:k]
+        expect[row] = idx[r, np.asarray(pos)[order]].tolist()
+
+    put("winners_last", np.arange(n_in - k, n_in), top)
+    put("winners_first", np.arange(k), top)
+    put("winners_first_scattered", np.sort(rng.permutation(E)[:k]), top)
+    r = CARRY_ROWS["tie_across_512"]
+    pos = np.arange(E - k, min(E + k, n_in))
+    idx[r, pos] = np.sort(idx[r, pos])[::-1]                    # descending spot index along the positions: the later, the better
+    val[r, pos] = 3.0
+    expect["tie_across_512"] = idx[r, pos[::-1][:k]].tolist()
+    assert idx[r, pos[-1]] < idx[r, pos[0]] and pos[-1] >= E > pos[0]
+    pads = np.zeros((n_rows, ld), dtype=bool)
+    pads[CARRY_ROWS["pads_interleaved"], 0::2] = True
+    pads[CARRY_ROWS["first_chunk_all_pads"], :E] = True
+    pads[CARRY_ROWS["later_chunk_all_pads"], E:2 * E] = True
+    r = CARRY_ROWS["fewer_than_k"]
+    real = np.concatenate([rng.permutation(E)[:(k - 1) // 2], E + rng.permutation(n_in - E)[:min(k - 1 - (k - 1) // 2, n_in - E)]]).astype(int)
+    pads[r] = True
+    pads[r, real] = False
+    pads[CARRY_ROWS["none_real"]] = True
+    small = np.array([1e-40, -1e-40, 1.4e-45, -1.4e-45, 0.0, -0.0, -1.0, 2.0 ** -126], dtype=np.float32)
+    assert (np.abs(small[:4]) > 0).all() and (np.abs(small[:4]) < 2.0 ** -126).all() and np.signbit(small[5])
+    last = n_in - 1 if n_in - 1 > E else 400                   # (513: position 512 is the last one)
+    put("signs_zeros_denormals", np.array([3, E - 1, E, last, 100, E - 2, 7, 300]), small)
+    r = CARRY_ROWS["zeros_across_512"]
+    pos = np.array([10, 20, E - 1, E, last])
+    idx[r, pos] = np.sort(idx[r, pos])[[3, 1, 4, 0, 2]]        # the lowest spot index sits behind position 512, on a -0.0
+    val[r, pos] = np.array([0.0, -0.0, 0.0, -0.0, -0.0], dtype=np.float32)
+    order = np.argsort(idx[r, pos])[:k]
+    expect["zeros_across_512"] = idx[r, pos[order]].tolist()
+    idx[pads] = -1
+    val[pads] = 9.0
+    expect["none_real"] = [-1] * k
+    rv, ri = merge_reference(val[:, :n_in], idx[:, :n_in], k)
+    n_real = len(real)
+    assert n_real < k and (ri[CARRY_ROWS["fewer_than_k"], :n_real] >= 0).all() and (ri[CARRY_ROWS["fewer_than_k"], n_real:] == -1).all()
+    expect["fewer_than_k"] = ri[CARRY_ROWS["fewer_than_k"]].tolist()
+    assert (ri[CARRY_ROWS["first_chunk_all_pads"]] >= 0).sum() == min(k, n_in - E)
+    for row in ("later_chunk_all_pads", "pads_interleaved"):
+        assert (ri[CARRY_ROWS[row]] >= 0).all(), row
+    return val, idx, expect
 
 
 def check_shards(device, world, V, k, C=40, K=5, n=3):
