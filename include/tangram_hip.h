@@ -312,6 +312,34 @@ int tg_planes_consistency(const float* const* planes_dev, int32_t n_runs, int64_
                           void* workspace_dev, double* pearson_out_dev, float* vote_entropy_out_dev,
                           float* consensus_entropy_out_dev, int32_t* votes_out_dev, void* hip_stream);
 
+/* The same question over SPOT SHARDS (every rank holds a block of the columns of every plane), in three steps:
+ *  1. each rank writes a PACKET of 8-byte units, [nm moment sums][n_rows consensus sums][R][n_rows] argmax words {key(p), ~global
+ *     column}, nm = R + R (R + 1) / 2 (tg_consistency_packet_bytes(R, n_rows); n_rows = 0: the moment sums alone).  The shift of the
+ *     moments is 1 / (total columns); p of a handle is the value its tg_mapper_result writes, from the global row statistics.
+ *       tg_mapper_consistency_shard  R handles of one shard geometry (cells, local spots, pitch, total spots, spot offset, stream);
+ *                                    a shard needs its communicator attached (TG_ERR_STATE otherwise); a block one spot wide is
+ *                                    legal, only total spots >= 2 is required.  Unsharded handles are taken too (one rank).
+ *       tg_planes_consistency_shard  R float planes, n_rows x n_cols local columns of n_cols_total, the first at col_offset.
+ *                                    with_rows = 0: the packet holds the moment sums only, col_offset is not used and n_cols_total only
+ *                                    sets the shift (it must be the same on every rank) -- what a correlation of planes sharded along
+ *                                    any axis needs, since the moments of the flattened planes are additive.
+ *     workspace_dev: tg_consistency_query_bytes(R, n_rows) bytes, 8-byte aligned like the packet.
+ *  2. the caller gathers the W packets in rank order (any transport), packet_stride_bytes apart.
+ *  3. tg_consistency_merge answers, identically on every rank, everything in ascending rank order: votes = the maximum of the ranks'
+ *     words (equal p on two ranks: the lower global column), vote entropy from the merged votes, consensus entropy = the fp64 sum
+ *     of the ranks' sums times 1 / ln(n_cols_total), pearson from the summed moments with N = n_elem (elements of a whole plane),
+ *     pairs in np.tril_indices(R, -1) order.  Each output may be NULL, not all; n_rows = 0 gives pearson alone.
+ * Asynchronous, no allocation, fixed orders, no atomics.  TG_ERR_INVALID, never a fault, for NULL or misaligned buffers, R, W, sizes or
+ * strides out of range.  tg_mapper_consistency itself keeps refusing a shard.                                                        */
+int tg_consistency_packet_bytes(int32_t n_runs, int64_t n_rows, size_t* bytes_out);
+int tg_mapper_consistency_shard(tg_mapper* const* mappers, int32_t n_runs, void* workspace_dev, void* packet_out_dev);
+int tg_planes_consistency_shard(const float* const* planes_dev, int32_t n_runs, int64_t n_rows, int64_t n_cols, int64_t ld,
+                                int64_t n_cols_total, int64_t col_offset, int32_t with_rows, void* workspace_dev, void* packet_out_dev,
+                                void* hip_stream);
+int tg_consistency_merge(const void* packets_dev, int32_t n_ranks, int32_t n_runs, int64_t n_rows, int64_t packet_stride_bytes,
+                         int64_t n_cols_total, int64_t n_elem, double* pearson_out_dev, float* vote_entropy_out_dev,
+                         float* consensus_entropy_out_dev, int32_t* votes_out_dev, void* hip_stream);
+
 /* ---- per-gene scores of projected against measured expression ------------------------------------------------------------------
  * What compare_spatial_geneexp reports per gene (utils.py:424-426: one dot product and one np.linalg.norm pair per gene over a
  * spots x genes plane on the host), from two float planes on the device, pred_dev[n_spots][ld_pred] and meas_dev[n_spots][ld_meas];
@@ -329,6 +357,15 @@ int tg_planes_consistency(const float* const* planes_dev, int32_t n_runs, int64_
 int tg_gene_scores_query_bytes(int64_t n_spots, int32_t n_genes, size_t* bytes_out);
 int tg_gene_scores(const float* pred_dev, int64_t ld_pred, const float* meas_dev, int64_t ld_meas, int64_t n_spots,
                    int32_t n_genes, void* workspace_dev, double* moments_out_dev, double* score_out_dev, void* hip_stream);
+
+/* Spot shards: every rank calls tg_gene_scores on its own rows of the two planes and keeps moments_out_dev; the caller gathers the W
+ * sets in rank order into moments_ranks_dev, double [W][3][n_genes], and this call merges them on every rank: each moment of a gene
+ * is the sum over the ranks in ASCENDING rank order, starting from rank 0's value (W = 1 returns its input's bits), the score is
+ * dot / (sqrt(pp) sqrt(gg)) formed as tg_gene_scores forms it; a zero norm gives NaN.  The same gathered input gives the same bits
+ * on every rank.  Either output may be NULL, not both; moments_out_dev may not overlap moments_ranks_dev.  No workspace; enqueued
+ * on `hip_stream`.  TG_ERR_INVALID, never a fault: a NULL or misaligned (8 bytes) input, both outputs NULL, W < 1, n_genes < 1.     */
+int tg_gene_scores_merge(const double* moments_ranks_dev, int32_t n_ranks, int32_t n_genes, double* moments_out_dev,
+                         double* score_out_dev, void* hip_stream);
 
 /* ---- batched independent mappings ------------------------------------------------------------------------------
  * The reference trains independent mappings one after the other: one per held-out gene in `cross_val` (utils.py:576-600; 249 in

@@ -5,7 +5,7 @@ from .mapping_optimizer import Mapper, MapperConstrained          # noqa: F401
 from .mapping_utils import map_cells_to_space, adata_to_cluster_expression, density_priors  # noqa: F401
 from . import preprocess                                          # noqa: F401
 from .utils import project_genes, compare_spatial_geneexp, score_genes       # noqa: F401
-from .gene_score import gene_scores, GeneScorer                   # noqa: F401
+from .gene_score import gene_scores, gene_scores_sharded, GeneScorer, ShardedGeneScorer   # noqa: F401
 from .sparse_project import project_sparse, SparseMap             # noqa: F401
 from .batched import train_many, MapperBatch                                   # noqa: F401
 from .cross_validation import cross_val, cv_data_gen                        # noqa: F401

@@ -93,8 +93,13 @@ def _signatures():
         "tg_mapper_consistency": (i32, [P(vp), i32, vp, vp, vp, vp, vp]),
         "tg_planes_consistency": (i32, planes),
         "tg_debug_planes_consistency": (i32, planes + [i32]),
+        "tg_consistency_packet_bytes": (i32, [i32, i64, P(sz)]),
+        "tg_mapper_consistency_shard": (i32, [P(vp), i32, vp, vp]),
+        "tg_planes_consistency_shard": (i32, [P(vp), i32, i64, i64, i64, i64, i64, i32, vp, vp, vp]),
+        "tg_consistency_merge": (i32, [vp, i32, i32, i64, i64, i64, i64, vp, vp, vp, vp, vp]),
         "tg_gene_scores_query_bytes": (i32, [i64, i32, P(sz)]),
         "tg_gene_scores": (i32, [vp, i64, vp, i64, i64, i32, vp, vp, vp, vp]),
+        "tg_gene_scores_merge": (i32, [vp, i32, i32, vp, vp, vp]),
         "tg_batch_query_bytes": (sz, [i32]),
         "tg_batch_create": (i32, [P(vp), i32, vp, P(vp)]),
         "tg_batch_step": (i32, [vp, i32, f32, P(vp), i32]),

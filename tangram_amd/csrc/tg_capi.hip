@@ -2218,7 +2218,130 @@ static int tg_consist_launch(TgConsistArgs a, int mode, int n_runs, void* worksp
     });
     if (a.mom)
         TG_LAUNCH(tg_consist_finish, tg_shape(1, 1, 256, TG_CONSIST_FINISH_LDS), s, (const double*)a.mom, (int)n_parts, (int)n_runs,
-                  (double)a.n_rows * (double)a.n_cols, pearson);
+                  (double)a.n_rows * (double)a.n_cols, pearson, (double*)nullptr);
+    TG_LAUNCH_CK();
+    return TG_OK;
+}
+
+// ---- the same over spot shards: a packet per rank (tg_consist.h), merged by tg_consistency_merge
+extern "C" int tg_consistency_packet_bytes(int32_t n_runs, int64_t n_rows, size_t* bytes_out) {
+    if (!bytes_out) return tg_fail(TG_ERR_INVALID, "consistency packet: bytes_out is NULL");
+    if (n_runs < 1 || n_runs > TG_CONSIST_MAX_RUNS) return tg_fail(TG_ERR_INVALID, "consistency packet: %d runs are outside [1, %d]", n_runs, TG_CONSIST_MAX_RUNS);
+    if (n_rows < 0 || n_rows > 0x7fffffffLL) return tg_fail(TG_ERR_INVALID, "consistency packet: %lld rows are outside [0, 2^31 - 1]", (long long)n_rows);
+    *bytes_out = 8 * tg_consist_packet_units(n_runs, n_rows);
+    return TG_OK;
+}
+
+// validated: a.plane (+ rshift / rinvz), ld, n_rows, n_cols (local), spot_offset are set; rows: the packet carries the per-row part
+static int tg_consist_shard_launch(TgConsistArgs a, int mode, int n_runs, long long n_cols_total, bool rows, void* workspace_dev, void* packet_dev,
+                                   tg_stream_t s) {
+    const long long n_parts = tg_consist_parts(a.n_rows, TG_CONSIST_MAX_PARTS);
+    const int nm = tg_consist_nmom(n_runs);
+    a.inv_log_cols = 0.f;                                                // (not used by the shard form: the merge divides)
+    a.shift = 1.0 / (double)n_cols_total;
+    a.mom = n_runs > 1 ? (double*)workspace_dev : nullptr;
+    a.vote_ent = nullptr; a.cons_ent = nullptr; a.votes = nullptr;
+    double* packet = (double*)packet_dev;
+    a.row_cons = rows ? packet + nm : nullptr;
+    a.words = rows ? (unsigned long long*)packet + nm + a.n_rows : nullptr;
+    if (!a.mom && !rows) return TG_OK;                                   // one run, no rows: nothing to form
+    tg_with_runs(n_runs, [&](auto rr) {
+        constexpr int R = decltype(rr)::value;
+        const TgShape shape = tg_consist_rows_shape(n_parts, R);
+        if (mode == TG_CONSIST_LOGITS) TG_LAUNCH((tg_consist_rows<R, TG_CONSIST_LOGITS, true>), shape, s, a);
+        else if (mode == TG_CONSIST_VEC) TG_LAUNCH((tg_consist_rows<R, TG_CONSIST_VEC, true>), shape, s, a);
+        else TG_LAUNCH((tg_consist_rows<R, TG_CONSIST_SCALAR, true>), shape, s, a);
+    });
+    if (a.mom)
+        TG_LAUNCH(tg_consist_finish, tg_shape(1, 1, 256, TG_CONSIST_FINISH_LDS), s, (const double*)a.mom, (int)n_parts, (int)n_runs, 1.0,
+                  (double*)nullptr, packet);
+    else
+        TG_LAUNCH(tg_fill, tg_shape(1, 1, 256, 0), s, (float*)packet, (size_t)(2 * nm), 0.f);     // one run: no moment is formed, the packet's are zero
+    TG_LAUNCH_CK();
+    return TG_OK;
+}
+
+extern "C" int tg_mapper_consistency_shard(tg_mapper* const* mappers, int32_t n_runs, void* workspace_dev, void* packet_out_dev) {
+    if (!mappers) return tg_fail(TG_ERR_INVALID, "shard consistency: the handle array is NULL");
+    if (n_runs < 1 || n_runs > TG_CONSIST_MAX_RUNS) return tg_fail(TG_ERR_INVALID, "shard consistency: %d runs are outside [1, %d]", n_runs, TG_CONSIST_MAX_RUNS);
+    for (int i = 0; i < n_runs; ++i) {
+        if (!mappers[i]) return tg_fail(TG_ERR_INVALID, "shard consistency: handle %d is NULL", i);
+        if (!mappers[i]->ready) return tg_fail(TG_ERR_STATE, "shard consistency: handle %d is not ready", i);
+    }
+    const tg_mapper* m0 = mappers[0];
+    TgConsistArgs a;
+    memset(&a, 0, sizeof a);
+    for (int i = 0; i < n_runs; ++i) {
+        const tg_mapper* m = mappers[i];
+        if (m->L.Vtot != m->L.V && !m->comm)
+            return tg_fail(TG_ERR_STATE, "shard consistency: handle %d is a spot shard without a communicator: its row statistics are not global", i);
+        if (m->L.C != m0->L.C || m->L.V != m0->L.V || m->L.Vp != m0->L.Vp || m->L.Vtot != m0->L.Vtot || m->cfg.spot_offset != m0->cfg.spot_offset)
+            return tg_fail(TG_ERR_INVALID, "shard consistency: handle %d is %d cells x %d of %d spots at %d (pitch %d), handle 0 %d x %d of %d at %d (pitch %d)", i,
+                           m->L.C, m->L.V, m->L.Vtot, (int)m->cfg.spot_offset, m->L.Vp, m0->L.C, m0->L.V, m0->L.Vtot, (int)m0->cfg.spot_offset, m0->L.Vp);
+        if (m->stream != m0->stream) return tg_fail(TG_ERR_INVALID, "shard consistency: all handles must be created on the same stream");
+        a.plane[i] = (const float*)(m->st + m->L.s_M); a.rshift[i] = m->fp(m->L.o_rshift); a.rinvz[i] = m->fp(m->L.o_rinvz);
+    }
+    if (m0->L.Vtot < 2) return tg_fail(TG_ERR_INVALID, "shard consistency: %d spots in all: at least two columns (the entropies are divided by log(columns))", m0->L.Vtot);
+    if (m0->L.C < 1 || m0->L.V < 1 || m0->cfg.spot_offset < 0 || (long long)m0->cfg.spot_offset + m0->L.V > m0->L.Vtot)
+        return tg_fail(TG_ERR_INVALID, "shard consistency: the block of %d spots at %d does not lie inside the %d spots", m0->L.V, (int)m0->cfg.spot_offset, m0->L.Vtot);
+    if (!workspace_dev || !packet_out_dev || (((uintptr_t)workspace_dev | (uintptr_t)packet_out_dev) & 7))
+        return tg_fail(TG_ERR_INVALID, "shard consistency: the workspace or the packet is NULL or not 8-byte aligned");
+    a.ld = m0->L.Vp; a.n_rows = m0->L.C; a.n_cols = m0->L.V; a.spot_offset = m0->cfg.spot_offset;
+    return tg_consist_shard_launch(a, TG_CONSIST_LOGITS, n_runs, m0->L.Vtot, true, workspace_dev, packet_out_dev, m0->stream);
+}
+
+extern "C" int tg_planes_consistency_shard(const float* const* planes_dev, int32_t n_runs, int64_t n_rows, int64_t n_cols, int64_t ld,
+                                           int64_t n_cols_total, int64_t col_offset, int32_t with_rows, void* workspace_dev, void* packet_out_dev,
+                                           void* hip_stream) {
+    if (!planes_dev) return tg_fail(TG_ERR_INVALID, "shard planes consistency: the plane array is NULL");
+    if (n_runs < 1 || n_runs > TG_CONSIST_MAX_RUNS) return tg_fail(TG_ERR_INVALID, "shard planes consistency: %d runs are outside [1, %d]", n_runs, TG_CONSIST_MAX_RUNS);
+    if (n_rows < 1 || n_cols < 1 || ld < n_cols || n_rows > 0x7fffffffLL || n_cols > 0x7fffffffLL - 2 * TG_CONSIST_CHUNK)
+        return tg_fail(TG_ERR_INVALID, "shard planes consistency: %lld rows x %lld columns (pitch %lld): at least one of each, a pitch of at least the columns, 32-bit indices",
+                       (long long)n_rows, (long long)n_cols, (long long)ld);
+    if (n_cols_total < 2 || n_cols_total > 0x7fffffffLL - 2 * TG_CONSIST_CHUNK)
+        return tg_fail(TG_ERR_INVALID, "shard planes consistency: %lld columns in all: at least two, below 2^31", (long long)n_cols_total);
+    if (with_rows && (col_offset < 0 || col_offset + n_cols > n_cols_total))
+        return tg_fail(TG_ERR_INVALID, "shard planes consistency: the block of %lld columns at %lld does not lie inside the %lld columns", (long long)n_cols,
+                       (long long)col_offset, (long long)n_cols_total);
+    TgConsistArgs a;
+    memset(&a, 0, sizeof a);
+    bool vec = ld % 4 == 0;
+    for (int i = 0; i < n_runs; ++i) {
+        if (!planes_dev[i]) return tg_fail(TG_ERR_INVALID, "shard planes consistency: plane %d is NULL", i);
+        a.plane[i] = planes_dev[i];
+        vec = vec && ((uintptr_t)planes_dev[i] & 15) == 0;
+    }
+    if (!workspace_dev || !packet_out_dev || (((uintptr_t)workspace_dev | (uintptr_t)packet_out_dev) & 7))
+        return tg_fail(TG_ERR_INVALID, "shard planes consistency: the workspace or the packet is NULL or not 8-byte aligned");
+    a.ld = ld; a.n_rows = (int)n_rows; a.n_cols = (int)n_cols; a.spot_offset = with_rows ? (int)col_offset : 0;
+    return tg_consist_shard_launch(a, vec ? TG_CONSIST_VEC : TG_CONSIST_SCALAR, n_runs, n_cols_total, with_rows != 0, workspace_dev, packet_out_dev,
+                                   (tg_stream_t)hip_stream);
+}
+
+extern "C" int tg_consistency_merge(const void* packets_dev, int32_t n_ranks, int32_t n_runs, int64_t n_rows, int64_t packet_stride_bytes,
+                                    int64_t n_cols_total, int64_t n_elem, double* pearson_out_dev, float* vote_entropy_out_dev,
+                                    float* consensus_entropy_out_dev, int32_t* votes_out_dev, void* hip_stream) {
+    if (n_ranks < 1) return tg_fail(TG_ERR_INVALID, "consistency merge: %d ranks: at least one", (int)n_ranks);
+    if (n_runs < 1 || n_runs > TG_CONSIST_MAX_RUNS) return tg_fail(TG_ERR_INVALID, "consistency merge: %d runs are outside [1, %d]", n_runs, TG_CONSIST_MAX_RUNS);
+    if (n_rows < 0 || n_rows > 0x7fffffffLL) return tg_fail(TG_ERR_INVALID, "consistency merge: %lld rows are outside [0, 2^31 - 1]", (long long)n_rows);
+    if (n_cols_total < 2 || n_elem < 1) return tg_fail(TG_ERR_INVALID, "consistency merge: %lld columns and %lld elements in all: at least two columns, one element",
+                                                         (long long)n_cols_total, (long long)n_elem);
+    if (!packets_dev || ((uintptr_t)packets_dev & 7)) return tg_fail(TG_ERR_INVALID, "consistency merge: the packets are NULL or not 8-byte aligned");
+    if (packet_stride_bytes % 8 != 0 || packet_stride_bytes < (int64_t)(8 * tg_consist_packet_units(n_runs, n_rows)))
+        return tg_fail(TG_ERR_INVALID, "consistency merge: a packet stride of %lld bytes is no multiple of 8 or shorter than the packet of %lld bytes",
+                       (long long)packet_stride_bytes, (long long)(8 * tg_consist_packet_units(n_runs, n_rows)));
+    const bool pearson = pearson_out_dev && n_runs > 1;
+    const bool rows = n_rows > 0 && (vote_entropy_out_dev || consensus_entropy_out_dev || votes_out_dev);
+    if (!pearson && !rows) return tg_fail(TG_ERR_INVALID, "consistency merge: every output is NULL (or has nothing to hold)");
+    TgConsistMergeArgs a;
+    a.packets = (const unsigned long long*)packets_dev; a.stride = packet_stride_bytes / 8; a.n_ranks = n_ranks; a.n_rows = (int)n_rows;
+    a.inv_log_cols = (float)(1.0 / log((double)n_cols_total)); a.n_elem = (double)n_elem;
+    a.pearson = pearson ? pearson_out_dev : nullptr;
+    a.vote_ent = rows ? vote_entropy_out_dev : nullptr; a.cons_ent = rows ? consensus_entropy_out_dev : nullptr; a.votes = rows ? (int*)votes_out_dev : nullptr;
+    tg_with_runs(n_runs, [&](auto rr) {
+        constexpr int R = decltype(rr)::value;
+        TG_LAUNCH((tg_consist_merge<R>), tg_consist_merge_shape(rows ? n_rows : 0), (tg_stream_t)hip_stream, a);
+    });
     TG_LAUNCH_CK();
     return TG_OK;
 }
@@ -2341,6 +2464,29 @@ extern "C" int tg_gene_scores(const float* pred_dev, int64_t ld_pred, const floa
     if (vec) TG_LAUNCH((tg_score_partials<true>), shape, s, a);
     else TG_LAUNCH((tg_score_partials<false>), shape, s, a);
     TG_LAUNCH(tg_score_finish, tg_score_finish_shape(n_genes), s, (const double*)a.part, (int)n_slabs, (int)n_genes, moments_out_dev, score_out_dev);
+    TG_LAUNCH_CK();
+    return TG_OK;
+}
+
+// spot shards: the W ranks' moments[3][n_genes] (tg_gene_scores on each rank's own rows, gathered by the caller) -> the moments and
+// scores of the whole plane, summed in ascending rank order
+extern "C" int tg_gene_scores_merge(const double* moments_ranks_dev, int32_t n_ranks, int32_t n_genes, double* moments_out_dev,
+                                    double* score_out_dev, void* hip_stream) {
+    if (n_ranks < 1 || n_genes < 1)
+        return tg_fail(TG_ERR_INVALID, "gene scores merge: %d ranks x %d genes: at least one of each", (int)n_ranks, (int)n_genes);
+    if (!moments_ranks_dev || ((uintptr_t)moments_ranks_dev & 7))
+        return tg_fail(TG_ERR_INVALID, "gene scores merge: the ranks' moments are NULL or not 8-byte aligned");
+    if (!moments_out_dev && !score_out_dev) return tg_fail(TG_ERR_INVALID, "gene scores merge: every output is NULL");
+    if ((((uintptr_t)moments_out_dev | (uintptr_t)score_out_dev) & 7))
+        return tg_fail(TG_ERR_INVALID, "gene scores merge: an output is not 8-byte aligned");
+    {   // an output inside the input would be summed after it was overwritten
+        const uintptr_t in0 = (uintptr_t)moments_ranks_dev, in1 = in0 + (size_t)n_ranks * 3 * (size_t)n_genes * 8;
+        const uintptr_t m0 = (uintptr_t)moments_out_dev, s0 = (uintptr_t)score_out_dev;
+        if ((m0 && m0 < in1 && m0 + 3 * (size_t)n_genes * 8 > in0) || (s0 && s0 < in1 && s0 + (size_t)n_genes * 8 > in0))
+            return tg_fail(TG_ERR_INVALID, "gene scores merge: an output overlaps the ranks' moments");
+    }
+    TG_LAUNCH(tg_score_merge, tg_score_merge_shape(n_genes), (tg_stream_t)hip_stream, moments_ranks_dev, (int)n_ranks, (int)n_genes, moments_out_dev,
+              score_out_dev);
     TG_LAUNCH_CK();
     return TG_OK;
 }

@@ -30,6 +30,9 @@
 //                        r_ab = cov_ab / sqrt(var_a var_b), cov_ab = S_ab - S_a S_b / N, N = n_rows n_cols, for the pairs in the
 //                        order of np.tril_indices(R, -1): (1,0), (2,0), (2,1), (3,0) ...  A plane of zero variance gives 0 / 0.
 //
+//   tg_consist_rows<R, MODE, true> / tg_consist_merge<R>   the same over spot shards: a packet per rank, merged in rank order (at the
+//                        end of this file).
+//
 // Shape of tg_consist_rows (that of tg_row_topk): the row is taken in chunks of TG_CONSIST_CHUNK columns that live in registers, all
 // R x TG_CONSIST_NQ loads of a chunk issued before the first use, non-temporal, each element read once.  R is a template argument
 // (1 .. TG_CONSIST_MAX_RUNS): the loaded quads, the argmax keys and the R + R (R + 1) / 2 + 1 double accumulators (45 at R = 8) are
@@ -70,6 +73,10 @@ struct TgConsistArgs {
     float* vote_ent;                                    // [n_rows] or null
     float* cons_ent;                                    // [n_rows] or null
     int* votes;                                         // [R][n_rows] or null
+    // shard form (tg_consist_rows<R, MODE, true>): n_cols are the LOCAL columns, spot_offset the global index of column 0; shift and
+    // inv_log_cols are those of the TOTAL number of columns; nothing finished is written, vote_ent / cons_ent / votes are not read
+    unsigned long long* words;                          // [R][n_rows] argmax words {key(p), ~global column}, or null
+    double* row_cons;                                   // [n_rows] sum_v m_v log m_v over the local columns, or null
 };
 
 // a float as an unsigned that orders like it; -0 as +0; >= 1 (0 is "no column")
@@ -113,7 +120,7 @@ TG_DEV unsigned long long tg_consist_wave_max(unsigned long long w) {
 
 static inline TgShape tg_consist_rows_shape(long long n_parts, int R) { return tg_shape(n_parts, 1, 256, tg_consist_rows_lds(R)); }
 
-template <int R, int MODE> TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_consist_rows(TgConsistArgs a) {
+template <int R, int MODE, bool SHARD = false> TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_consist_rows(TgConsistArgs a) {
     TG_LDS_DECL;
     constexpr int NM = R + R * (R + 1) / 2;
     double* wsum = (double*)tg_lds;                                     // [4][NM] the workgroup's moments, once
@@ -196,6 +203,21 @@ template <int R, int MODE> TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_consist_rows(
             if (lane == 0) mkey[wave * R + r] = w;
         }
         __syncthreads();
+        if (SHARD) {
+            // ---- shard form: the row's R words with the GLOBAL column behind the key, and its consensus sum as it stands
+            if (t == 0) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    unsigned long long w = mkey[r];
+#pragma unroll
+                    for (int u = 1; u < 4; ++u) { const unsigned long long o = mkey[u * R + r]; w = o > w ? o : w; }
+                    const unsigned gv = (unsigned)a.spot_offset + ~(unsigned)w;
+                    if (a.words) a.words[(size_t)r * a.n_rows + c] = (w & 0xffffffff00000000ull) | (unsigned long long)(~gv);
+                }
+                if (a.row_cons) a.row_cons[c] = ((ment[0] + ment[1]) + ment[2]) + ment[3];
+            }
+            continue;
+        }
         if (t == 0) {
             int vote[R];
 #pragma unroll
@@ -233,8 +255,9 @@ template <int R, int MODE> TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_consist_rows(
     if (t < NM) a.mom[(size_t)t * gridDim.x + blockIdx.x] = ((wsum[t] + wsum[NM + t]) + wsum[2 * NM + t]) + wsum[3 * NM + t];
 }
 
-// mom [nm][n_parts] -> pearson [R (R - 1) / 2]; one workgroup of 256 threads
-TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_consist_finish(const double* mom, int n_parts, int R, double n_elem, double* pearson) {
+// mom [nm][n_parts] -> pearson [R (R - 1) / 2] (or null) and / or the sums themselves, sums [nm] (or null: the shard form asks for them);
+// one workgroup of 256 threads
+TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_consist_finish(const double* mom, int n_parts, int R, double n_elem, double* pearson, double* sums) {
     TG_LDS_DECL;
     double* red = (double*)tg_lds;                                      // [256]
     double* fin = red + 256;                                            // [nm]
@@ -252,7 +275,8 @@ TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_consist_finish(const double* mom, int n_
         if (t == 0) fin[j] = red[0];
         __syncthreads();
     }
-    if (t < R * (R - 1) / 2) {
+    if (sums && t < nm) sums[t] = fin[t];                               // shard form: the local sums, no correlation
+    if (pearson && t < R * (R - 1) / 2) {
         int g = 1;                                                      // pair t of np.tril_indices(R, -1): (g, h), g > h
         while (g * (g + 1) / 2 <= t) ++g;
         const int h = t - g * (g - 1) / 2;
@@ -260,5 +284,79 @@ TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_consist_finish(const double* mom, int n_
         const double cov = fin[tg_consist_pair(R, h, g)] - sg * sh / n_elem;
         const double vg = fin[tg_consist_pair(R, g, g)] - sg * sg / n_elem, vh = fin[tg_consist_pair(R, h, h)] - sh * sh / n_elem;
         pearson[t] = cov / sqrt(vg * vh);
+    }
+}
+
+// ---- spot shards ------------------------------------------------------------------------------------------------------------------
+// Every rank holds a block of the columns.  tg_consist_rows<R, MODE, true> + tg_consist_finish(sums) leave a PACKET of 8-byte units,
+//   [nm moment sums][n_rows consensus sums][R][n_rows] argmax words        (tg_consist_packet_units; n_rows = 0: the moments alone)
+// with shift and the entropies' divisor taken from the TOTAL number of columns and the global column behind every key.  The W packets
+// are gathered in rank order, and tg_consist_merge<R> answers on every rank, everything in ascending rank order:
+//   votes              the maximum of the ranks' words: equal p on two ranks goes to the lower global column
+//   vote entropy       from the merged votes, as tg_consist_rows forms it
+//   consensus entropy  -(float)(rank-order fp64 sum of the consensus sums) * 1 / ln(total columns)
+//   pearson            from the rank-order sums of the moments with N = n_elem, pairs in np.tril_indices(R, -1) order (workgroup 0)
+// A thread per row; R is a template argument: the votes live in registers.
+TG_HD size_t tg_consist_packet_units(int R, long long n_rows) { return (size_t)tg_consist_nmom(R) + (size_t)n_rows * (size_t)(1 + R); }
+
+struct TgConsistMergeArgs {
+    const unsigned long long* packets;                  // [W][stride] 8-byte units
+    long long stride;
+    int n_ranks, n_rows;
+    float inv_log_cols;                                 // 1 / ln(total columns)
+    double n_elem;                                      // elements of a whole plane
+    double* pearson;                                    // [R (R - 1) / 2] or null
+    float* vote_ent;                                    // [n_rows] or null
+    float* cons_ent;                                    // [n_rows] or null
+    int* votes;                                         // [R][n_rows] or null
+};
+
+static inline TgShape tg_consist_merge_shape(long long n_rows) { return tg_shape(n_rows > 0 ? (n_rows + 255) / 256 : 1, 1, 256, 0); }
+
+TG_DEV double tg_consist_rank_sum(const TgConsistMergeArgs& a, size_t unit) {
+    const double* p = (const double*)a.packets + unit;
+    double s = p[0];
+    for (int w = 1; w < a.n_ranks; ++w) s += p[(size_t)w * (size_t)a.stride];      // ascending ranks
+    return s;
+}
+
+template <int R> TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_consist_merge(TgConsistMergeArgs a) {
+    constexpr int NM = R + R * (R + 1) / 2;
+    const int t = threadIdx.x;
+    if (blockIdx.x == 0 && a.pearson && t < R * (R - 1) / 2) {
+        int g = 1;                                                      // pair t of np.tril_indices(R, -1): (g, h), g > h
+        while (g * (g + 1) / 2 <= t) ++g;
+        const int h = t - g * (g - 1) / 2;
+        const double sg = tg_consist_rank_sum(a, g), sh = tg_consist_rank_sum(a, h);
+        const double cov = tg_consist_rank_sum(a, tg_consist_pair(R, h, g)) - sg * sh / a.n_elem;
+        const double vg = tg_consist_rank_sum(a, tg_consist_pair(R, g, g)) - sg * sg / a.n_elem;
+        const double vh = tg_consist_rank_sum(a, tg_consist_pair(R, h, h)) - sh * sh / a.n_elem;
+        a.pearson[t] = cov / sqrt(vg * vh);
+    }
+    const long long c = (long long)blockIdx.x * 256 + t;
+    if (c >= a.n_rows) return;
+    if (a.cons_ent) a.cons_ent[c] = -(float)tg_consist_rank_sum(a, (size_t)NM + (size_t)c) * a.inv_log_cols;
+    if (!a.votes && !a.vote_ent) return;
+    int vote[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const unsigned long long* p = a.packets + (size_t)NM + (size_t)a.n_rows * (size_t)(1 + r) + (size_t)c;
+        unsigned long long w = p[0];
+        for (int k = 1; k < a.n_ranks; ++k) { const unsigned long long o = p[(size_t)k * (size_t)a.stride]; w = o > w ? o : w; }
+        vote[r] = (int)~(unsigned)w;
+        if (a.votes) a.votes[(size_t)r * a.n_rows + c] = vote[r];
+    }
+    if (a.vote_ent) {
+        float ve = 0.f;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            int n = 0;
+            bool first = true;
+#pragma unroll
+            for (int u = 0; u < R; ++u)
+                if (vote[u] == vote[r]) { ++n; if (u < r) first = false; }
+            if (first) { const float f = (float)n / (float)R; ve -= f * tg_log(f); }
+        }
+        a.vote_ent[c] = ve * a.inv_log_cols;
     }
 }

@@ -22,6 +22,8 @@
 //                        round (the loads run side by side), then ONE thread per gene and moment adds the round's slabs to its sum in
 //                        ASCENDING slab order -> moments[3][n_genes] (dot, pp, gg) and score = dot / (sqrt(pp) sqrt(gg)) in fp64
 //                        (IEEE square root and division).  A zero norm gives 0 / 0 = NaN, as the reference does.
+//   tg_score_merge       spot shards: the moments[3][n_genes] of W ranks, gathered -> their sums in ascending rank order and the score of
+//                        the whole plane, formed as tg_score_finish forms it (at the end of this file).
 // No atomics, fixed orders: the same inputs give the same bits on every call.  Rows and columns outside the planes enter as
 // fma(0, 0, sum) = sum, which changes no bit (a sum starts at +0 and never becomes -0).
 #pragma once
@@ -153,4 +155,29 @@ TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_score_finish(const double* part, int n_s
     }
     __syncthreads();
     if (score && t < NG && g < n_genes) score[g] = fin[l] / (sqrt(fin[NG + l]) * sqrt(fin[2 * NG + l]));
+}
+
+// ---- spot shards: every rank reduces its own rows to moments[3][n_genes] (tg_score_finish), the W sets are gathered, and this kernel
+// merges them: a thread per gene adds each of its three moments over the ranks in ASCENDING rank order, starting from rank 0's value
+// (not from 0: one rank returns its bits), and ends as tg_score_finish ends.  Neighbouring threads read neighbouring doubles.
+// in [W][3][n_genes] -> moments [3][n_genes] (or null), score [n_genes] (or null)
+static inline TgShape tg_score_merge_shape(long long n_genes) { return tg_shape((n_genes + 255) / 256, 1, 256, 0); }
+
+TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_score_merge(const double* in, int n_ranks, int n_genes, double* moments, double* score) {
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= n_genes) return;
+    const size_t n = (size_t)n_genes;
+    double s[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) s[j] = in[(size_t)j * n + (size_t)g];
+    for (int r = 1; r < n_ranks; ++r) {                                 // ascending ranks
+        const double* p = in + (size_t)r * 3 * n + (size_t)g;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) s[j] += p[(size_t)j * n];
+    }
+    if (moments) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) moments[(size_t)j * n + (size_t)g] = s[j];
+    }
+    if (score) score[g] = s[0] / (sqrt(s[1]) * sqrt(s[2]));
 }

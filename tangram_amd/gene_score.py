@@ -4,6 +4,8 @@ what `compare_spatial_geneexp` computes with one `np.linalg.norm` pair per gene 
   gene_scores     score[j] = <pred[:, j], meas[:, j]> / (|pred[:, j]| |meas[:, j]|) for two planes of equal shape, float64; optionally the
                   three moments (dot, |pred|^2, |meas|^2) they are made of
   GeneScorer      the workspace and outputs of planes of one height, reused block of genes by block of genes
+  gene_scores_sharded / ShardedGeneScorer   the same over planes whose spots are spread over the ranks of a communicator: local
+                  moments, one all-gather of [3, n_genes] doubles, a merge in rank order (tg_gene_scores_merge)
   GeneBlocks      selected gene columns of an AnnData matrix (dense or scipy-sparse) as dense float32 device blocks
 
 Every element is converted to double, products and sums are fp64 in an order that depends on the number of spots alone: a column
@@ -71,6 +73,57 @@ def gene_scores(pred, meas, *, moments=False, device=None):
     pred, meas = _plane(pred, device, "pred"), _plane(meas, device, "meas")
     n_spots, n = (int(s) for s in pred.shape)
     scorer = GeneScorer(n_spots, n, device)
+    score = torch.empty(n, dtype=torch.float64, device=device)
+    mom = torch.empty((3, n), dtype=torch.float64, device=device) if moments else None
+    scorer.score_into(pred, meas, score, mom)
+    return (score, mom) if moments else score
+
+
+class ShardedGeneScorer:
+    """GeneScorer over spot shards (collective: every rank of `comm` makes the same calls with planes of the same width): this rank
+    holds `n_spots_local` rows of both planes.  Per call the rank reduces its rows to moments (tg_gene_scores), the [3, n] doubles of
+    all ranks are gathered once through `comm.all_gather(outs, t)`, and every rank merges them in rank order (tg_gene_scores_merge):
+    the same bits on every rank, no plane taller than the rank's own spots anywhere."""
+
+    def __init__(self, n_spots_local, max_genes, comm, device):
+        self.local = GeneScorer(n_spots_local, max_genes, device)
+        self.device, self.max_genes, self.comm, self.world = self.local.device, int(max_genes), comm, int(comm.world)
+        self._mine = torch.empty(3 * self.max_genes, dtype=torch.float64, device=self.device)
+        self._every = torch.empty(self.world * 3 * self.max_genes, dtype=torch.float64, device=self.device)
+
+    def score_into(self, pred, meas, score=None, moments=None):
+        """As GeneScorer.score_into on this rank's rows; `score` [n] and `moments` [3, n] are those of ALL spots."""
+        n = int(pred.shape[1])
+        if n < 1 or n > self.max_genes:
+            raise ValueError(f"this scorer takes planes of 1 to {self.max_genes} genes, not {n} (the same width on every rank)")
+        for t, shape, name in ((score, (n,), "score"), (moments, (3, n), "moments")):
+            if t is not None and (t.dtype != torch.float64 or t.device != self.device or tuple(t.shape) != shape or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous float64 tensor of shape {shape} on {self.device}")
+        if score is None and moments is None:
+            raise ValueError("score and moments are both None")
+        mine = self._mine[:3 * n].view(3, n)
+        self.local.score_into(pred, meas, None, mine)
+        every = self._every[:self.world * 3 * n].view(self.world, 3, n)
+        self.comm.all_gather(list(every.unbind(0)), mine)
+        call(self.device, _capi.lib().tg_gene_scores_merge, every.data_ptr(), self.world, n, moments.data_ptr() if moments is not None else None,
+             score.data_ptr() if score is not None else None, stream(self.device))
+
+
+def gene_scores_sharded(pred_local, meas_local, comm, moments=False, *, device=None):
+    """`gene_scores` of planes whose rows (spots) are spread over the ranks of `comm` (anything with `world` and
+    `all_gather(outs, t)`: a ShardedMapperEngine's `pycomm`); collective.  pred_local, meas_local: this rank's rows
+    [n_spots_local, n_genes], the same genes on every rank.  Returns on every rank the same float64 device tensor [n_genes] of the
+    scores over ALL spots; `moments=True`: (scores, moments [3, n_genes]), each moment the ranks' sums added in rank order."""
+    if device is None:
+        device = next((t.device for t in (pred_local, meas_local) if isinstance(t, torch.Tensor) and t.device.type == "cuda"), None)
+        if device is None:
+            device = next((t.device for t in (pred_local, meas_local) if isinstance(t, torch.Tensor)), torch.device("cuda:0"))
+    device = check_device(device)
+    if tuple(pred_local.shape) != tuple(meas_local.shape):
+        raise ValueError(f"pred is {tuple(pred_local.shape)}, meas is {tuple(meas_local.shape)}: the two planes must have the same shape")
+    pred, meas = _plane(pred_local, device, "pred"), _plane(meas_local, device, "meas")
+    n_spots, n = (int(s) for s in pred.shape)
+    scorer = ShardedGeneScorer(n_spots, n, comm, device)
     score = torch.empty(n, dtype=torch.float64, device=device)
     mom = torch.empty((3, n), dtype=torch.float64, device=device) if moments else None
     scorer.score_into(pred, meas, score, mom)

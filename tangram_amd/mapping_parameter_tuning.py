@@ -14,6 +14,9 @@ still resident when the question is asked: one pass over them (tg_mapper_consist
 the votes and both entropies per cell; nothing C x V is written or copied.  The three metric functions keep the reference's
 names, arguments and return shapes and run through the same kernel on plain planes (tg_planes_consistency).
 
+Spot-sharded mappers (all of one group) are answered from per-rank packets merged in rank order (tg_mapper_consistency_shard,
+tg_consistency_merge): collective, the same bits on every rank, nothing cells x spots gathered.
+
 Differences to the reference, all of them documented where they occur: values are float32 on the device (a float64 cube is
 cast), `pearson_corr` of a single run raises instead of returning an empty array, and `train_multiple_Mapper` RETURNS the metrics
 (the reference hands them to `ray.train.report`; wrap the call for a ray trial).
@@ -135,16 +138,97 @@ def consensus_entropy(pred_probs_cube, device=None):
 
 def _engine_of(m):
     if getattr(m, "_sharded", None) is not None:
-        raise NotImplementedError("mapping_consistency of spot-sharded mappers is not available")
+        return m._sharded.eng
     return getattr(m, "_engine", m)
+
+
+def _shard_group(mappers):
+    """None for mappers that hold every spot; the first mapper's ShardedMapperEngine when ALL are spot shards.  Mixed: ValueError."""
+    if not mappers:
+        raise ValueError("no mapper")
+    sharded = [getattr(m, "_sharded", None) for m in mappers]
+    if all(s is None for s in sharded):
+        return None
+    if any(s is None for s in sharded):
+        raise ValueError("mapping_consistency takes mappers that are all spot-sharded over one group or all unsharded, not a mixture")
+    s0 = sharded[0]
+    if any(s.world != s0.world or s.rank != s0.rank or s.n_spots_total != s0.n_spots_total for s in sharded):
+        raise ValueError("spot-sharded mappers must be shards of one group: the same world, rank and total number of spots")
+    return s0
+
+
+def _gather_packets(sh, packet):
+    """The ranks' packets (int64 device tensors of one length) side by side, in rank order: [world, len]."""
+    every = torch.empty((sh.world, packet.numel()), dtype=torch.int64, device=packet.device)
+    sh.pycomm.all_gather(list(every.unbind(0)), packet)
+    return every
+
+
+def _merge(lib, dev, every, r, n_rows, n_cols_total, n_elem, out):
+    ptr = lambda k: out[k].data_ptr() if k in out else None
+    call(dev, lib.tg_consistency_merge, every.data_ptr(), int(every.shape[0]), r, n_rows, int(every.stride(0)) * 8, int(n_cols_total), int(n_elem),
+         ptr("pearson"), ptr("vote_entropy"), ptr("consensus_entropy"), ptr("votes"), stream(dev))
+    return out
+
+
+def _sharded_mapper_consistency(sh, engines, votes):
+    """Collective: every rank reduces its own block of spots to a packet (tg_mapper_consistency_shard), the packets are gathered once
+    through the group's Python communicator, and every rank merges them in rank order (tg_consistency_merge)."""
+    e0 = engines[0]
+    lib, dev, r, C = e0._lib, e0.device, len(engines), int(e0.C)
+    sh.checked()
+    ws = workspace(lib.tg_consistency_query_bytes, r, C, device=dev, min_bytes=8)
+    nbytes = ct.c_size_t()
+    _capi.check(lib.tg_consistency_packet_bytes(r, C, ct.byref(nbytes)))
+    packet = torch.empty(nbytes.value // 8, dtype=torch.int64, device=dev)
+    arr = (ct.c_void_p * r)(*[e._h for e in engines])
+    e0._call(lib.tg_mapper_consistency_shard, arr, r, ws.data_ptr(), packet.data_ptr(), tensors=(ws, packet))
+    every = _gather_packets(sh, packet)
+    out = {"vote_entropy": torch.empty(C, dtype=torch.float32, device=dev),
+           "consensus_entropy": torch.empty(C, dtype=torch.float32, device=dev)}
+    if r > 1:
+        out["pearson"] = torch.empty(r * (r - 1) // 2, dtype=torch.float64, device=dev)
+    if votes:
+        out["votes"] = torch.empty((r, C), dtype=torch.int32, device=dev)
+    V = int(sh.n_spots_total)
+    return _merge(lib, dev, every, r, C, V, C * V, out)
+
+
+def sharded_planes_pearson(planes_local, comm_owner, n_rows_total):
+    """Pairwise Pearson correlations of r planes whose ROWS are spread over the ranks (collective): planes_local are this rank's
+    [rows_local, j] blocks; the moments of the flattened planes are additive over row blocks, so every rank reduces its block
+    (tg_planes_consistency_shard, moments only), the sums are gathered and merged in rank order -> float64 device tensor
+    [r (r - 1) / 2], the same bits on every rank.  `comm_owner`: a ShardedMapperEngine (its `pycomm`, `world`)."""
+    planes, dev = _planes(planes_local, None)
+    r = len(planes)
+    if r < 2:
+        raise ValueError("pearson_corr needs at least two runs")
+    lib = _capi.lib()
+    j = int(planes[0].shape[1])
+    planes = _flat(planes)
+    n_rows, n_cols = (int(x) for x in planes[0].shape)
+    ws = workspace(lib.tg_consistency_query_bytes, r, n_rows, device=dev, min_bytes=8)
+    nbytes = ct.c_size_t()
+    _capi.check(lib.tg_consistency_packet_bytes(r, 0, ct.byref(nbytes)))
+    packet = torch.empty(nbytes.value // 8, dtype=torch.int64, device=dev)
+    arr = (ct.c_void_p * r)(*[p.data_ptr() for p in planes])
+    call(dev, lib.tg_planes_consistency_shard, arr, r, n_rows, n_cols, int(planes[0].stride(0)) if n_rows > 1 else max(int(planes[0].stride(0)), n_cols),
+         max(j, 2), 0, 0, ws.data_ptr(), packet.data_ptr(), stream(dev))
+    every = _gather_packets(comm_owner, packet)
+    out = {"pearson": torch.empty(r * (r - 1) // 2, dtype=torch.float64, device=dev)}
+    return _merge(lib, dev, every, r, 0, max(j, 2), int(n_rows_total) * j, out)["pearson"]
 
 
 def mapper_consistency(mappers, votes=False):
     """tg_mapper_consistency over trained mappers (or engines) whose logits are resident: dict of device tensors like
-    `planes_consistency`, of the mappings softmax(M) -- the bits `result()` would hold, which is never formed."""
+    `planes_consistency`, of the mappings softmax(M) -- the bits `result()` would hold, which is never formed.
+    Mappers that all carry `_sharded` from one group (spot shards): collective, every rank gets the same outputs for ALL spots, votes as
+    global spot indices; no rank reads anything but its own logits.  Mixing sharded and unsharded mappers raises ValueError."""
+    mappers = list(mappers)
+    sh = _shard_group(mappers)
     engines = [_engine_of(m) for m in mappers]
-    if not engines:
-        raise ValueError("no mapper")
+    if sh is not None:
+        return _sharded_mapper_consistency(sh, engines, votes)
     e0 = engines[0]
     lib, dev, r = e0._lib, e0.device, len(engines)
     ws = workspace(lib.tg_consistency_query_bytes, r, e0.C, device=dev, min_bytes=8)
@@ -169,8 +253,12 @@ def mapping_consistency(mappers, S_val=None):
         gene_expr_consistency (with `S_val` [n_cells, n_val], host or device): mean pairwise Pearson correlation of the runs'
         projections softmax(M)^T S_val ([n_spots, n_val], `engine.project_genes`, at the mapper's gemm precision).
 
-    Nothing of size cells x spots is written or copied.  A single mapper has no pair: its consistencies are NaN."""
+    Nothing of size cells x spots is written or copied.  A single mapper has no pair: its consistencies are NaN.
+    Spot-sharded mappers (all of them, one group; collective): the same numbers on every rank; `gene_expr_consistency` from each
+    rank's own [local_spots, n_val] projections, nothing gathered but a few sums."""
+    mappers = list(mappers)
     out = mapper_consistency(mappers)
+    sh = _shard_group(mappers)
     nan = float("nan")
     res = {"cell_map_consistency": float(out["pearson"].cpu().numpy().mean()) if "pearson" in out else nan,
            "cell_map_agreement": float(1.0 - out["vote_entropy"].cpu().numpy().astype(np.float64).mean()),
@@ -179,7 +267,11 @@ def mapping_consistency(mappers, S_val=None):
         engines = [_engine_of(m) for m in mappers]
         if len(engines) > 1:
             S_val = S_val if hasattr(S_val, "tocsr") else torch.as_tensor(S_val).to(device=engines[0].device, dtype=torch.float32)
-            res["gene_expr_consistency"] = float(pearson_corr([e.project_genes(S_val) for e in engines]).mean())
+            proj = [e.project_genes(S_val) for e in engines]
+            if sh is not None:
+                res["gene_expr_consistency"] = float(sharded_planes_pearson(proj, sh, sh.n_spots_total).cpu().numpy().mean())
+            else:
+                res["gene_expr_consistency"] = float(pearson_corr(proj).mean())
         else:
             res["gene_expr_consistency"] = nan
     return res

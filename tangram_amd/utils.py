@@ -245,8 +245,31 @@ class _Route:
             self._engine = None
 
 
+class _ShardRoute:
+    """The route of `score_genes(..., distributed=True)`: `project(S)` is THIS rank's block of spots only, [hi - lo, n_genes]
+    (the engine's `project_genes` on the rank's own logits; nothing is gathered); `rows` = (lo, hi) of `shard_bounds`, `n_spots` the
+    total, `comm` the mapper's communicator."""
+
+    def __init__(self, mapper, n_cells):
+        from .sharded import shard_bounds
+        sh = mapper._sharded
+        engine = sh.eng
+        self.device, self.n_spots, self.comm = engine.device, int(sh.n_spots_total), sh.pycomm
+        self.rows = shard_bounds(self.n_spots, sh.world, sh.rank, sh.spatial)
+        if engine.C != n_cells:
+            raise ValueError("The two AnnDatas need to have same `obs` index.")
+        sh.checked()
+        self._project = lambda S: engine.project_genes(S, unfiltered=True)      # softmax(M) without the filter, like adata_map.X
+
+    def project(self, S):
+        return self._project(S)
+
+    def release(self):
+        pass
+
+
 def score_genes(adata_map, adata_sc, adata_sp, cluster_label=None, scale=True, genes=None, *, mapper=None, truncated=False,
-                device="cuda:0", gemm_precision="bf16x3", gene_block=1024):
+                device="cuda:0", gemm_precision="bf16x3", gene_block=1024, distributed=False):
     """`compare_spatial_geneexp(project_genes(adata_map, adata_sc, cluster_label, scale, ...), adata_sp, adata_sc, genes)` without the
     projected plane: the same DataFrame (index, columns, `is_training`, sparsities, order), but no spots x genes array ever exists on
     the host and none wider than `gene_block` genes on the device.  `adata_sc` is prepared as project_genes prepares it; only the
@@ -254,16 +277,31 @@ def score_genes(adata_map, adata_sc, adata_sp, cluster_label=None, scale=True, g
     matrix are gathered on the device (a dense matrix is uploaded once; a scipy-sparse one as CSR), projected by the route the
     keywords select exactly as in project_genes (`mapper=`: the mapping resident in HBM; a dense `adata_map.X`; `truncated=True`: the
     sparse `adata_map.X` itself; the same ValueErrors), and scored against the same genes of `adata_sp.X` (tg_gene_scores), the
-    scratch reused.  A spot-sharded mapper is refused with a ValueError."""
+    scratch reused.  A spot-sharded mapper is refused with a ValueError unless `distributed=True`.
+    `distributed=True` (the keyword of `Mapper` and `map_cells_to_space`; collective: every rank makes the same call with the same
+    full `adata_sc` / `adata_sp` and its own spot-sharded `mapper`): per block of genes a rank projects onto its OWN spots only,
+    scores them against its own rows `lo:hi` of `adata_sp.X` (`shard_bounds`), and the ranks exchange `[3, gene_block]` doubles -- the
+    local dot products and squared norms, summed in rank order on every rank (tg_gene_scores_merge).  Every rank returns the same
+    DataFrame; no rank holds a plane taller than its own spots.  ValueError with a mapper that is not spot-sharded or with
+    `truncated=True`."""
     from . import preprocess as pre
-    from .gene_score import GeneBlocks, GeneScorer
+    from .gene_score import GeneBlocks, GeneScorer, ShardedGeneScorer
     adata_sc_p, S_all = _prepare_sc(adata_map, adata_sc, cluster_label, scale)
     n_cells = int(S_all.shape[0])
-    if mapper is not None and not truncated and getattr(mapper, "_sharded", None) is not None:
-        raise ValueError("score_genes does not take a spot-sharded mapper: every rank holds the moments of its own spots only, and "
-                         "their exchange is not available; project with project_genes and score with compare_spatial_geneexp")
-    route = _Route(adata_map, n_cells, mapper, truncated, device, gemm_precision)
+    sharded = mapper is not None and getattr(mapper, "_sharded", None) is not None
+    if distributed:
+        if truncated or not sharded:
+            raise ValueError("score_genes(distributed=True) scores over the spot shards of a mapper made with distributed=True: pass that "
+                             "mapper as mapper=, without truncated=True")
+        route = _ShardRoute(mapper, n_cells)
+    else:
+        if sharded and not truncated:
+            raise ValueError("score_genes does not take a spot-sharded mapper without distributed=True: every rank holds the moments of its "
+                             "own spots only; pass distributed=True on every rank (the ranks then exchange the moments), or project "
+                             "with project_genes and score with compare_spatial_geneexp")
+        route = _Route(adata_map, n_cells, mapper, truncated, device, gemm_precision)
     dev, n_spots = route.device, route.n_spots
+    lo, hi = route.rows if distributed else (0, n_spots)
     try:
         overlap_genes = _check_score_inputs(adata_sc_p.uns, adata_sp, genes)
         mu.annotate_gene_sparsity(adata_sp)
@@ -272,15 +310,16 @@ def score_genes(adata_map, adata_sc, adata_sp, cluster_label=None, scale=True, g
         var_ge = adata_sc_p.var.copy()
         var_ge["is_training"] = var_ge.index.isin(adata_map.uns["train_genes_df"].index.values)
         idx_sc = _columns_of(var_ge, overlap_genes, "adata_sc")
-        sp_ = GeneBlocks(adata_sp.X, _columns_of(adata_sp.var, overlap_genes, "adata_sp"), dev)
+        X_sp = adata_sp.X[lo:hi] if distributed else adata_sp.X                      # a shard measures against its own rows only
+        sp_ = GeneBlocks(X_sp, _columns_of(adata_sp.var, overlap_genes, "adata_sp"), dev)
         n = len(overlap_genes)
         kb = max(1, min(int(gene_block), n))
         scores = torch.empty(n, dtype=torch.float64, device=dev)
         if n:
             sparse_s = hasattr(S_all, "tocsr")
             S_dev = pre.DeviceCSR(S_all, dev) if sparse_s else torch.as_tensor(S_all).to(device=dev, dtype=torch.float32)
-            scorer = GeneScorer(n_spots, kb, dev)
-            meas = torch.empty((n_spots, kb), dtype=torch.float32, device=dev)
+            scorer = ShardedGeneScorer(hi - lo, kb, route.comm, dev) if distributed else GeneScorer(n_spots, kb, dev)
+            meas = torch.empty((hi - lo, kb), dtype=torch.float32, device=dev)
             for k0 in range(0, n, kb):
                 kc = min(kb, n - k0)
                 cols = idx_sc[k0:k0 + kc]
