@@ -373,7 +373,14 @@ int tg_gene_scores_merge(const double* moments_ranks_dev, int32_t n_ranks, int32
  * of ONE shape / configuration together: every kernel of the iteration is launched once with blockIdx.z = mapping (its arguments
  * come from arrays in `scratch_dev`, tg_batch_query_bytes(B) bytes of device memory).  The handles stay usable on their own
  * (result, project, state); they must share the stream they were created on and stay at the same step.  Results are the bits of
- * stepping each handle alone.  Handles of ONE class (all Mapper or all MapperConstrained), without spatial terms, rows <= 16 384 spots.
+ * stepping each handle alone.  Handles of ONE class (all Mapper or all MapperConstrained), rows <= 16 384 spots.
+ * Spatial terms (Mapper): a batch holds handles with ONE set of terms -- the same of neighbourhood / cell-type islands /
+ * autocorrelation, the same number of cell types and the same of Getis-Ord / Moran / Geary switched on; the lambdas' VALUES and
+ * the spot graphs are per handle (every handle owns its CSR copies).  Such a batch follows the solo step launch by launch, each
+ * kernel as its batched twin (tg_spmm_b, tg_ct_*_b, tg_ac_*_b, tg_loss_finalize_b ahead of the emitter with `extra`).
+ * Refused (TG_ERR_UNSUPPORTED / TG_ERR_INVALID, tg_last_error names the reason; nothing is written): mixed sets of terms, spot
+ * shards, the band pipeline, rows longer than 16 384 spots, a backward tile edge other than the layout's on handles with spatial
+ * terms, and -- WITHOUT spatial terms only, where the emitter keeps its coefficients in LDS -- more than 6 128 padded gene columns.
  * history_dev: host array of B device pointers (one history buffer per mapping) or NULL.
  * A batch steps its handles as 2 - 4 groups side by side: group 0 on the handles' stream, the others on
  * streams the batch creates (hipStreamNonBlocking; destroyed by tg_batch_destroy).  Every tg_batch_step forks them from the

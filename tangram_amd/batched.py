@@ -10,9 +10,12 @@ Clusters-mode problems are tiny (18 x 250 x 9852) and launch-bound on a 256-CU G
 per-mapping kernel arguments into device arrays and adds a batch index to the grid of every kernel of the iteration
 (blockIdx.z = mapping).  Results are the bits of training the same mappings one by one: nothing is shared between them.
 `Mapper`s batch with `Mapper`s, `MapperConstrained`s with `MapperConstrained`s (utils.py:576-600 passes any `mode`).
-Mappings that are not batched (a shape of their own, spatial terms, more than 16 384 spots, more than 2^25 cells x spots -- one
-such mapping fills the GPU and a batch of them measured slower than one after the other --, or a group the C library
-refuses) are trained by one host thread per mapping (the C ABI releases the GIL; different handles may be driven from different
+Mappings with spatial terms (neighbourhood, cell-type islands, Getis-Ord / Moran / Geary) batch with mappings that have the SAME
+set of terms and the same number of cell types; the lambdas' values and the spot graphs may differ per mapping (the tuning trial:
+three seeds with lambda_neighborhood_g1, lambda_ct_islands, lambda_getis_ord).
+Mappings that are not batched (a shape or a set of spatial terms of their own, spot shards, the band pipeline, more than 16 384
+spots, more than 2^25 cells x spots -- one such mapping fills the GPU and a batch of them measured slower than one after the
+other --, or a group the C library refuses) are trained by one host thread per mapping (the C ABI releases the GIL; different handles may be driven from different
 threads); `batched=False` additionally gives every mapping a HIP stream of its own.
 """
 from __future__ import annotations
@@ -68,12 +71,15 @@ class MapperBatch:
 ROWPASS_MAX_SPOTS = 16384          # TG_ROWPASS_MAX_V (tg_capi.hip): rows the single-kernel update holds in registers
 BATCH_MAX_ELEMENTS = 1 << 25       # cells x spots above which ONE mapping fills the GPU: batching then LOSES (measured, B = 2 - 4 vs one
                                    # after the other: 4 200 x 1 100: 1.4 - 1.75x, 8 000 x 3 000: 1.05 - 1.13x, 12 000 x 5 000: 0.96 - 0.98x,
-                                   # 26 431 x 9 852: 0.83 - 0.85x; profiles/r03/run15_batch_sizes)
+                                   # 26 431 x 9 852: 0.83 - 0.85x; profiles/r03/run15_batch_sizes).  Mappers with spatial terms keep
+                                   # this bound: three seeds with nb + ct + Getis-Ord in one batch vs one after the other measured
+                                   # 2.27x at 2 000 x 2 000, 2.01x at 4 200 x 1 100 and 1.65x at 8 000 x 4 000 (32 M, just under the
+                                   # bound); nothing above it was measured (profiles/batched_spatial/bench_batched_spatial.json)
 EMIT_MAX_GENE_COLS = 6128          # (2 Kp + 32) floats of dynamic LDS <= 48 KB in tg_dghat_emit<SELF>: Kp = rup(K + 1, tile) <= 6128
 
 
 def _gene_cols(e):
-    """Kp of the handle's layout: its K + 1 operand columns rounded up to the tile (no cell-type columns: no spatial terms here)."""
+    """Kp of a handle WITHOUT spatial terms: its K + 1 operand columns rounded up to the tile (no cell-type columns)."""
     if e.K + 1 + 255 <= EMIT_MAX_GENE_COLS:                 # fits whatever the tile (128 or 256)
         return e.K + 1
     geo = (ct.c_int * 8)()
@@ -88,16 +94,24 @@ def _batch_key(m):
     if type(m).__name__ not in ("Mapper", "MapperConstrained") or e is None or getattr(m, "_sharded", None) is not None:
         return None
     c = e.cfg
-    if c.lambda_neighborhood_g1 or c.lambda_ct_islands or c.lambda_getis_ord or c.lambda_moran or c.lambda_geary:
+    # the spatial terms that are on (tg_make_layout: has_nb, has_ct, has_ac) and which autocorrelation terms: a batch holds ONE set
+    ac = (c.lambda_getis_ord > 0, c.lambda_moran > 0, c.lambda_geary > 0)
+    terms = (c.lambda_neighborhood_g1 > 0, c.lambda_ct_islands > 0, any(ac)) + ac
+    spatial = any(terms)
+    if spatial and type(m).__name__ != "Mapper":                # (MapperConstrained ignores the spatial terms; the library refuses them there)
         return None
     if e.C * e.V > BATCH_MAX_ELEMENTS:
         return None
-    if e.V > ROWPASS_MAX_SPOTS or c.pipeline_bands > 1 or _gene_cols(e) > EMIT_MAX_GENE_COLS:
+    if e.V > ROWPASS_MAX_SPOTS or c.pipeline_bands > 1:
         return None
+    # (with spatial terms the emitter reads its coefficients from memory: no bound on the gene columns)
+    if not spatial and _gene_cols(e) > EMIT_MAX_GENE_COLS:
+        return None
+    n_types = int(getattr(c, "n_cell_types", 0)) if terms[1] else 0
     stream = e._torch_stream.cuda_stream if e._torch_stream is not None else 0
     # (effective_precision: folds built with s_exact="auto" whose S differs in bf16-exactness run different GEMM kernels)
     return (type(m).__name__, e.C, e.K, e.V, e.precision, getattr(e, "effective_precision", e.precision), bool(c.lambda_r or c.lambda_l1 or c.lambda_l2), str(e.device), stream,
-            c.beta1, c.beta2, c.tile_size, c.fwd_splits)
+            c.beta1, c.beta2, c.tile_size, c.fwd_splits, terms, n_types)
 
 
 def _train_batched(mappers, num_epochs, learning_rate, val_each=None):
@@ -148,7 +162,7 @@ def train_many(builders, num_epochs, learning_rate=0.1, max_concurrent=4, device
     builders: callables, each returning a `Mapper` / `MapperConstrained`.  They are called one after the other on the
               calling thread (the reference's initialisation draws from the global NumPy RNG, `np.random.seed(random_state)`,
               which must not be interleaved).
-    batched:  "auto" (default): mappings that can share a `tg_batch` (one class, one shape, no spatial terms, <= 16 384 spots)
+    batched:  "auto" (default): mappings that can share a `tg_batch` (one class, one shape, one set of spatial terms, <= 16 384 spots)
               advance in ONE launch per kernel -- `val_each=k` (Mapper) included: the batch pauses at every validation epoch; the others -- and any group the C library refuses -- get a host
               thread each, their kernels sharing the common creation stream.  False: every mapper is created on a HIP stream
               of its own and trained by its own host thread (`max_concurrent` at a time): kernels of different mappings overlap.

@@ -725,25 +725,54 @@ static int tg_setup_spatial_derived(tg_mapper* m) {
     return TG_OK;
 }
 
+// ---- arguments of the per-iteration spatial launches: ONE statement each, for the solo step below and for tg_batch_upload ----
+// Y = (graph gph) A over the gene columns: the plain tg_spmm every use starts from
+static TgSpmmArgs tg_spmm_args(tg_mapper* m, int gph, const float* A, float* Y) {
+    const TgLayout& L = m->L;
+    TgSpmmArgs a = {};
+    a.W = tg_csr(m, gph); a.A = A; a.Y = Y; a.V = L.Vs; a.Kp = L.Kp; a.k_begin = 0; a.k_end = L.K;
+    return a;
+}
+// neighbourhood term: W Ghat -> Y, its per-gene statistics against W G, and extra[:, :K] = W^T (nbcoef0 * WG + nbcoef1 * W Ghat)
+static TgSpmmArgs tg_nb_spmm_args(tg_mapper* m) { return tg_spmm_args(m, 0, tg_sp_ghat(m), m->fp(m->L.o_Y)); }
+static TgColstatsArgs tg_nb_colstats_args(tg_mapper* m) {
+    const TgLayout& L = m->L;
+    return TgColstatsArgs{m->fp(L.o_Y), m->fp(L.o_WG), L.Vs, L.Kp, m->fp(L.o_nbpart)};
+}
+static TgGeneReduceArgs tg_nb_reduce_args(tg_mapper* m) {
+    const TgLayout& L = m->L;
+    return TgGeneReduceArgs{m->fp(L.o_nbpart), L.grb_s, L.Kp, m->fp(L.o_nbstat)};
+}
+static TgSpmmArgs tg_nb_grad_spmm_args(tg_mapper* m) {
+    const TgLayout& L = m->L;
+    TgSpmmArgs a = tg_spmm_args(m, 1, m->fp(L.o_WG), m->fp(L.o_extra));
+    a.B = m->fp(L.o_Y); a.ca = m->fp(L.o_nbcoef); a.cb = m->fp(L.o_nbcoef) + L.Kp;
+    return a;
+}
+// cell-type islands: tg_ct_mask walks N (`transposed` = false), tg_ct_grad N^T
+static TgCtArgs tg_ct_args(tg_mapper* m, bool transposed) {
+    const TgLayout& L = m->L;
+    TgCtArgs c;
+    c.N = tg_csr(m, transposed ? 3 : 2); c.Ghat = tg_sp_ghat(m); c.mask = m->fp(L.o_ctmask); c.ctpart = m->fp(L.o_ctpart);
+    c.extra = m->fp(L.o_extra); c.V = L.Vs; c.Kp = L.Kp; c.K = L.K; c.T = L.T_ct; c.Tp = L.Tp; c.lambda_ct = m->cfg.lambda_ct_islands;
+    return c;
+}
+static TgShape tg_ct_shape(int V) { return tg_shape(V, 1, 64, 0); }      // tg_ct_mask(_b), tg_ct_grad(_b): one wave per spot
+
 // spatial terms, per iteration, part 1 (before tg_loss_finalize): W Ghat and its per-gene statistics; ct-islands mask
 static int tg_launch_spatial_stats(tg_mapper* m) {
     const TgLayout& L = m->L;
     if (L.has_nb) {
-        TgSpmmArgs a = {};
-        a.W = tg_csr(m, 0); a.A = tg_sp_ghat(m); a.B = nullptr; a.ca = nullptr; a.cb = nullptr;
-        a.Y = m->fp(L.o_Y); a.V = L.Vs; a.Kp = L.Kp; a.k_begin = 0; a.k_end = L.K;
-        TG_LAUNCH(tg_spmm, tg_spmm_shape(L.Vs), m->stream, a);
-        TG_LAUNCH(tg_colstats, tg_spot_blocks_shape(L.Vs), m->stream, (const float*)m->fp(L.o_Y), (const float*)m->fp(L.o_WG), L.Vs, L.Kp, m->fp(L.o_nbpart));
-        TG_LAUNCH(tg_gene_reduce, tg_gene_reduce_shape(L.Kp, false), m->stream, (const float*)m->fp(L.o_nbpart), L.grb_s, L.Kp, m->fp(L.o_nbstat));
+        const TgColstatsArgs c = tg_nb_colstats_args(m);
+        const TgGeneReduceArgs r = tg_nb_reduce_args(m);
+        TG_LAUNCH(tg_spmm, tg_spmm_shape(L.Vs), m->stream, tg_nb_spmm_args(m));
+        TG_LAUNCH(tg_colstats, tg_spot_blocks_shape(L.Vs), m->stream, c.A, c.B, c.V, c.Kp, c.part);
+        TG_LAUNCH(tg_gene_reduce, tg_gene_reduce_shape(L.Kp, false), m->stream, r.genepart, r.nrb, r.Kp, r.genestat);
         tg_prof_mark(m, "tg_spatial_nb_stats");
     }
     if (L.has_ct) {
-        TgCtArgs c;
-        c.N = tg_csr(m, 2); c.Ghat = tg_sp_ghat(m); c.mask = m->fp(L.o_ctmask); c.ctpart = m->fp(L.o_ctpart);
-        c.extra = m->fp(L.o_extra); c.V = L.Vs; c.Kp = L.Kp; c.K = L.K; c.T = L.T_ct; c.Tp = L.Tp; c.lambda_ct = m->cfg.lambda_ct_islands;
-        TG_LAUNCH(tg_ct_mask, tg_shape(L.Vs, 1, 64, 0), m->stream, c);
-        c.N = tg_csr(m, 3);
-        TG_LAUNCH(tg_ct_grad, tg_shape(L.Vs, 1, 64, 0), m->stream, c);
+        TG_LAUNCH(tg_ct_mask, tg_ct_shape(L.Vs), m->stream, tg_ct_args(m, false));
+        TG_LAUNCH(tg_ct_grad, tg_ct_shape(L.Vs), m->stream, tg_ct_args(m, true));
         tg_prof_mark(m, "tg_spatial_ct");
     }
     return TG_OK;
@@ -763,17 +792,37 @@ static TgAcArgs tg_ac_args(tg_mapper* m, const float* X, bool setup, float* hist
     return a;
 }
 
+// the four tg_spmm uses and the three tg_stat_reduce uses of the autocorrelation terms
+static TgSpmmArgs tg_ac_y_spmm_args(tg_mapper* m, const TgAcArgs& a) {        // Y = Ws X, local Geary sums into D
+    TgSpmmArgs sp = tg_spmm_args(m, 4, a.X, m->fp(m->L.o_acY));
+    sp.E = m->fp(m->L.o_acD);
+    return sp;
+}
+static TgSpmmArgs tg_ac_z_spmm_args(tg_mapper* m, const TgAcArgs& a) { return tg_spmm_args(m, 5, a.X, m->fp(m->L.o_acZ)); }   // Z = Ws^T X (Geary)
+static TgSpmmArgs tg_ac_grad_spmm_args(tg_mapper* m, const TgAcArgs& a) {     // extra[:, :K] (+)= Ws^T B1 + D - cm
+    TgSpmmArgs sg = tg_spmm_args(m, 5, a.B1, m->fp(m->L.o_extra));
+    sg.accumulate = m->L.has_nb ? 1 : 0; sg.addD = a.D; sg.addc = a.cm;
+    return sg;
+}
+static TgStatReduceArgs tg_ac_reduce_args(tg_mapper* m, const TgAcArgs& a, int stage) {      // stage 1, 2; 3: the centering constant
+    const TgLayout& L = m->L;
+    if (stage == 1) return TgStatReduceArgs{a.part, L.grb_s, (int)TGAC_NSTAT, L.Kp, a.stat};
+    if (stage == 2) return TgStatReduceArgs{a.part, L.grb_s, 3, L.Kp, a.stat2};
+    return TgStatReduceArgs{a.cmpart, L.grb_s, 1, L.Kp, a.cm};
+}
+static void tg_launch_stat_reduce(tg_mapper* m, const TgStatReduceArgs& r) {
+    TG_LAUNCH(tg_stat_reduce, tg_stat_reduce_shape(r.Kp), m->stream, r.part, r.nparts, r.nstat, r.Kp, r.out);
+}
+
 // Y = Ws X (+ local Geary sums into D), first and second stage statistics
 static void tg_ac_indicators(tg_mapper* m, TgAcArgs& a) {
     const TgLayout& L = m->L;
-    const TgShape blocks = tg_spot_blocks_shape(L.Vs), reduce = tg_stat_reduce_shape(L.Kp);
-    TgSpmmArgs sp = {};
-    sp.W = tg_csr(m, 4); sp.A = a.X; sp.Y = m->fp(L.o_acY); sp.E = m->fp(L.o_acD); sp.V = L.Vs; sp.Kp = L.Kp; sp.k_begin = 0; sp.k_end = L.K;
-    TG_LAUNCH(tg_spmm, tg_spmm_shape(L.Vs), m->stream, sp);
+    const TgShape blocks = tg_spot_blocks_shape(L.Vs);
+    TG_LAUNCH(tg_spmm, tg_spmm_shape(L.Vs), m->stream, tg_ac_y_spmm_args(m, a));
     TG_LAUNCH(tg_ac_stats1, blocks, m->stream, a);
-    TG_LAUNCH(tg_stat_reduce, reduce, m->stream, (const float*)a.part, L.grb_s, (int)TGAC_NSTAT, L.Kp, a.stat);
+    tg_launch_stat_reduce(m, tg_ac_reduce_args(m, a, 1));
     TG_LAUNCH(tg_ac_stats2, blocks, m->stream, a);
-    TG_LAUNCH(tg_stat_reduce, reduce, m->stream, (const float*)a.part, L.grb_s, 3, L.Kp, a.stat2);
+    tg_launch_stat_reduce(m, tg_ac_reduce_args(m, a, 2));
 }
 
 static int tg_setup_autocorr(tg_mapper* m) {
@@ -799,19 +848,12 @@ static int tg_launch_autocorr(tg_mapper* m, float* hist_row) {
     const TgLayout& L = m->L;
     TgAcArgs a = tg_ac_args(m, tg_sp_ghat(m), false, hist_row);
     tg_ac_indicators(m, a);
-    if (a.lam_geary > 0.f) {
-        TgSpmmArgs sz = {};
-        sz.W = tg_csr(m, 5); sz.A = a.X; sz.Y = m->fp(L.o_acZ); sz.V = L.Vs; sz.Kp = L.Kp; sz.k_begin = 0; sz.k_end = L.K;
-        TG_LAUNCH(tg_spmm, tg_spmm_shape(L.Vs), m->stream, sz);
-    }
+    if (a.lam_geary > 0.f) TG_LAUNCH(tg_spmm, tg_spmm_shape(L.Vs), m->stream, tg_ac_z_spmm_args(m, a));
     TgAcFinArgs f; f.a = a; f.tnorm = m->fp(L.o_actnorm);
-    TG_LAUNCH(tg_ac_finalize, tg_shape(1, 1, 1024, 64), m->stream, f);
+    TG_LAUNCH(tg_ac_finalize, tg_ac_finalize_shape(), m->stream, f);
     TG_LAUNCH(tg_ac_grad, tg_spot_blocks_shape(L.Vs), m->stream, a);
-    TG_LAUNCH(tg_stat_reduce, tg_stat_reduce_shape(L.Kp), m->stream, (const float*)a.cmpart, L.grb_s, 1, L.Kp, a.cm);
-    TgSpmmArgs sg = {};       // extra[:, :K] (+)= Ws^T B1 + D - cm
-    sg.W = tg_csr(m, 5); sg.A = a.B1; sg.Y = m->fp(L.o_extra); sg.V = L.Vs; sg.Kp = L.Kp; sg.k_begin = 0; sg.k_end = L.K;
-    sg.accumulate = L.has_nb ? 1 : 0; sg.addD = a.D; sg.addc = a.cm;
-    TG_LAUNCH(tg_spmm, tg_spmm_shape(L.Vs), m->stream, sg);
+    tg_launch_stat_reduce(m, tg_ac_reduce_args(m, a, 3));
+    TG_LAUNCH(tg_spmm, tg_spmm_shape(L.Vs), m->stream, tg_ac_grad_spmm_args(m, a));
     tg_prof_mark(m, "tg_spatial_autocorr");
     return TG_OK;
 }
@@ -820,10 +862,7 @@ static int tg_launch_autocorr(tg_mapper* m, float* hist_row) {
 static int tg_launch_spatial_grad(tg_mapper* m) {
     const TgLayout& L = m->L;
     if (L.has_nb) {
-        TgSpmmArgs a = {};
-        a.W = tg_csr(m, 1); a.A = m->fp(L.o_WG); a.B = m->fp(L.o_Y); a.ca = m->fp(L.o_nbcoef); a.cb = m->fp(L.o_nbcoef) + L.Kp;
-        a.Y = m->fp(L.o_extra); a.V = L.Vs; a.Kp = L.Kp; a.k_begin = 0; a.k_end = L.K;
-        TG_LAUNCH(tg_spmm, tg_spmm_shape(L.Vs), m->stream, a);
+        TG_LAUNCH(tg_spmm, tg_spmm_shape(L.Vs), m->stream, tg_nb_grad_spmm_args(m));
         tg_prof_mark(m, "tg_spatial_nb_grad");
     }
     return TG_OK;
@@ -1051,6 +1090,7 @@ static void tg_loss_args(tg_mapper* m, float* hist_row, TgFinalizeArgs& f, TgEmi
     e.V = L.V; e.Vr = L.Vr; e.Kp = L.Kp; e.K = L.K; e.n_aug = 1 + L.T_ct;
     e.fin = f;
 }
+static bool tg_is_spatial(const TgLayout& L) { return L.has_nb || L.has_ct || L.has_ac; }
 static bool tg_emit_self_ok(const tg_mapper* m) {      // the emit kernel can derive its coefficients itself (no spatial terms, LDS fits)
     const TgLayout& L = m->L;
     return !(L.has_nb || L.has_ct || L.has_ac) && L.bands == 1 && (L.Vtot == L.V || m->comm) && tg_emit_self_fits(L.Kp);
@@ -1074,7 +1114,7 @@ static int tg_launch_loss(tg_mapper* m, float* hist_row) {
     m->fin_pending = false;
     int rcs = tg_launch_spatial_stats(m);
     if (rcs) return rcs;
-    TG_LAUNCH(tg_loss_finalize, tg_shape(1, 1, 1024, 16 * 5 * 4), m->stream, f);
+    TG_LAUNCH(tg_loss_finalize, tg_loss_finalize_shape(), m->stream, f);
     tg_prof_mark(m, "tg_loss_finalize");
     if ((rcs = tg_launch_spatial_grad(m))) return rcs;
     if (L.has_ac && (rcs = tg_launch_autocorr(m, hist_row))) return rcs;
@@ -1369,6 +1409,10 @@ struct tg_batch {
 struct TgBatchArrays {
     TgFwdArgs* fwd; TgGhatReduceArgs* ghat; TgGeneReduceArgs* gene; TgEmitArgs* emit; TgBwdArgs* bwd; TgUpdateArgs* upd;
     TgHistRegArgs* hreg; TgFilterArgs* filt; TgMergeArgs* merge; float** scr; TgSmallArgs* small;
+    // spatial terms (filled for handles that have them), in the order of their launches; one array per USE of tg_spmm / tg_stat_reduce
+    TgSpmmArgs* nb_spmm; TgColstatsArgs* nb_cols; TgGeneReduceArgs* nb_red; TgCtArgs* ct_mask; TgCtArgs* ct_grad; TgFinalizeArgs* fin;
+    TgSpmmArgs* nb_grad; TgSpmmArgs* ac_y; TgAcArgs* ac; TgStatReduceArgs* ac_red1; TgStatReduceArgs* ac_red2; TgSpmmArgs* ac_z;
+    TgAcFinArgs* ac_fin; TgStatReduceArgs* ac_red3; TgSpmmArgs* ac_gsp;
     size_t bytes;
 };
 static TgBatchArrays tg_batch_arrays(unsigned char* base, int n) {
@@ -1376,6 +1420,8 @@ static TgBatchArrays tg_batch_arrays(unsigned char* base, int n) {
     size_t off = 0;
     auto take = [&](auto*& p) { p = (std::remove_reference_t<decltype(p)>)((uintptr_t)base + off); off += rup((size_t)n * sizeof *p, 256); };
     take(a.fwd); take(a.ghat); take(a.gene); take(a.emit); take(a.bwd); take(a.upd); take(a.hreg); take(a.filt); take(a.merge); take(a.scr); take(a.small);
+    take(a.nb_spmm); take(a.nb_cols); take(a.nb_red); take(a.ct_mask); take(a.ct_grad); take(a.fin); take(a.nb_grad); take(a.ac_y); take(a.ac);
+    take(a.ac_red1); take(a.ac_red2); take(a.ac_z); take(a.ac_fin); take(a.ac_red3); take(a.ac_gsp);
     a.bytes = off;
     return a;
 }
@@ -1388,15 +1434,32 @@ extern "C" int tg_batch_create(tg_mapper* const* mappers, int n, void* scratch_d
         const tg_mapper* m = mappers[i];
         if (!m || !m->ready) return tg_fail(TG_ERR_STATE, "mapper %d of the batch is not ready", i);
         const TgLayout &A = m->L, &B = m0->L;
+        // Spatial terms: a batch holds mappings with ONE set of terms (the launches of a step are the same for all of them); the lambdas'
+        // values and the graphs are per mapping (every handle owns its CSR copies and its argument blocks).
+        const bool sp = tg_is_spatial(A);
+        if (A.has_nb != B.has_nb || A.has_ct != B.has_ct || A.has_ac != B.has_ac || A.T_ct != B.T_ct || A.Tp != B.Tp ||
+            (m->cfg.lambda_getis_ord > 0.f) != (m0->cfg.lambda_getis_ord > 0.f) || (m->cfg.lambda_moran > 0.f) != (m0->cfg.lambda_moran > 0.f) ||
+            (m->cfg.lambda_geary > 0.f) != (m0->cfg.lambda_geary > 0.f))
+            return tg_fail(TG_ERR_INVALID, "mapper %d has another set of spatial terms (or another number of cell types) than mapper 0: a batch holds "
+                           "mappings with ONE set of terms", i);
         if (A.C != B.C || A.K != B.K || A.V != B.V || A.prec != B.prec || A.T != B.T || A.nsplit != B.nsplit || A.fwd_units != B.fwd_units || A.full != B.full)
             return tg_fail(TG_ERR_INVALID, "mapper %d differs in shape / precision / terms from mapper 0 (a batch is B mappings of ONE shape)", i);
         if (m->stream != m0->stream) return tg_fail(TG_ERR_INVALID, "all mappers of a batch must be created on the same stream");
         if (m->step != m0->step) return tg_fail(TG_ERR_INVALID, "all mappers of a batch must be at the same step");
         if (m->cfg.mode != m0->cfg.mode) return tg_fail(TG_ERR_INVALID, "a batch holds handles of ONE class (Mapper or MapperConstrained)");
-        if (m->comm || A.Vtot != A.V || A.bands > 1 || !tg_emit_self_ok(m) || A.V > TG_ROWPASS_MAX_V)
-            return tg_fail(TG_ERR_UNSUPPORTED, "mapper %d uses spatial terms, spot shards, the band pipeline, rows longer than %d spots or more genes "
-                           "than the emitter holds (%d padded gene columns, at most %d: K <= %d on 128 tiles, %d on 256)", i, TG_ROWPASS_MAX_V, A.Kp,
-                           tg_emit_self_kp_max(), tg_emit_self_kp_max() / 128 * 128 - 1, tg_emit_self_kp_max() / 256 * 256 - 1);
+        if (m->comm || A.Vtot != A.V || A.sp_shard)
+            return tg_fail(TG_ERR_UNSUPPORTED, "mapper %d is a spot shard: a batch holds whole mappings", i);
+        if (A.bands > 1) return tg_fail(TG_ERR_UNSUPPORTED, "mapper %d runs the band pipeline (pipeline_bands = %d): a batch steps on one stream per group", i, A.bands);
+        if (A.V > TG_ROWPASS_MAX_V)
+            return tg_fail(TG_ERR_UNSUPPORTED, "mapper %d has rows longer than %d spots: a batch updates with the one-kernel update only", i, TG_ROWPASS_MAX_V);
+        if (sp && m->cfg.mode != TG_MODE_MAPPER) return tg_fail(TG_ERR_UNSUPPORTED, "mapper %d: spatial terms exist only in Mapper", i);
+        // (spatial terms: the emitter takes its coefficients from memory and needs no dynamic LDS -- no limit on the genes beyond the layout's)
+        if (sp && A.bwd_T != A.T)
+            return tg_fail(TG_ERR_UNSUPPORTED, "mapper %d runs its backward GEMM on %d-spot tiles under the %d layout (bwd_tile): a batch with spatial terms "
+                           "steps on the layout's tiles only", i, A.bwd_T, A.T);
+        if (!sp && !tg_emit_self_ok(m))
+            return tg_fail(TG_ERR_UNSUPPORTED, "mapper %d has more genes than the emitter holds (%d padded gene columns, at most %d: K <= %d on 128 tiles, "
+                           "%d on 256)", i, A.Kp, tg_emit_self_kp_max(), tg_emit_self_kp_max() / 128 * 128 - 1, tg_emit_self_kp_max() / 256 * 256 - 1);
         if (m->cfg.beta1 != m0->cfg.beta1 || m->cfg.beta2 != m0->cfg.beta2) return tg_fail(TG_ERR_INVALID, "Adam betas differ inside the batch");
         for (int j = 0; j < i; ++j) if (mappers[j] == m) return tg_fail(TG_ERR_INVALID, "mapper %d appears twice in the batch", i);
     }
@@ -1470,6 +1533,25 @@ static int tg_batch_upload(tg_batch* b, float* const* hist) {
             A.merge[i] = tg_merge_args(m, m->fp(L.o_rowpair), 1, true, false, nullptr, 0);
         }
         A.scr[i] = m->fp(L.o_scal);
+        if (!tg_is_spatial(L)) continue;
+        // Spatial terms: the step follows the solo non-self path (tg_launch_loss).  tg_loss_finalize_b starts the history row ahead of the
+        // emitter, so the update kernel has no history workgroup; every kernel that writes the row gets the history BASE here and the
+        // row from TgStepVar (no history: the mapping's scratch row, like the solo step).
+        A.upd[i].fin_on = 0;
+        A.fin[i] = f;
+        if (L.has_nb) {
+            A.nb_spmm[i] = tg_nb_spmm_args(m); A.nb_cols[i] = tg_nb_colstats_args(m); A.nb_red[i] = tg_nb_reduce_args(m);
+            A.nb_grad[i] = tg_nb_grad_spmm_args(m);
+        }
+        if (L.has_ct) { A.ct_mask[i] = tg_ct_args(m, false); A.ct_grad[i] = tg_ct_args(m, true); }
+        if (L.has_ac) {
+            TgAcArgs a = tg_ac_args(m, tg_sp_ghat(m), false, nullptr);
+            a.hist = hist ? hist[i] : nullptr;
+            A.ac[i] = a;
+            A.ac_y[i] = tg_ac_y_spmm_args(m, a); A.ac_z[i] = tg_ac_z_spmm_args(m, a); A.ac_gsp[i] = tg_ac_grad_spmm_args(m, a);
+            A.ac_red1[i] = tg_ac_reduce_args(m, a, 1); A.ac_red2[i] = tg_ac_reduce_args(m, a, 2); A.ac_red3[i] = tg_ac_reduce_args(m, a, 3);
+            A.ac_fin[i].a = a; A.ac_fin[i].tnorm = m->fp(L.o_actnorm);
+        }
     }
     TG_CK(tg_memcpy_h2d(b->dev, b->stage, b->total, s));          // one copy, asynchronous (page-locked source that outlives the call)
     tg_event_record(b->e_upload, s);
@@ -1495,6 +1577,7 @@ static int tg_batch_step_impl(tg_batch* b, int n_steps, float lr, float* const* 
     const TgBwdTiles bt = tg_bwd_tiles(L, 0, L.nct, L.T);
     const TgBatchArrays A = tg_batch_arrays(b->dev, n);
     const bool want_vox = (m0->cfg.lambda_g2 != 0.f);
+    const bool spatial = tg_is_spatial(L);              // (all handles of the batch have the same terms: tg_batch_create)
     const int NG = b->n_groups, n_all = n;
     if (NG > 1) {                                    // fork: the groups' streams start behind everything already on the handles' stream
         tg_event_record(b->e_fork, m0->stream);
@@ -1505,6 +1588,10 @@ static int tg_batch_step_impl(tg_batch* b, int n_steps, float lr, float* const* 
         const int z0 = (int)((long long)grp * n_all / NG), n = (int)((long long)(grp + 1) * n_all / NG) - z0;     // this group's mappings
         tg_stream_t s = grp == 0 ? m0->stream : b->sub[grp - 1];
         const TgUpdateArgs* a_up = A.upd + z0; const TgSmallArgs* a_sm = A.small + z0;
+        const TgAdamStep as = tg_adam_step(m0->cfg, m0->step, lr);
+        TgStepVar var;
+        var.step_size = as.step_size; var.bc2_sqrt = as.bc2_sqrt;
+        var.hist_row = hist ? (long long)(first_row + it) : -1;
         if (L.smallc) {
 #define TG_SC_FWD_B(CM, VX) TG_LAUNCH_Z((tg_sc_forward_b<CM, VX>), tg_sc_forward_shape(L.V, L.Kp), n, s, a_sm)
             TG_SC_DISPATCH(L.C, want_vox, TG_SC_FWD_B);
@@ -1524,20 +1611,42 @@ static int tg_batch_step_impl(tg_batch* b, int n_steps, float lr, float* const* 
                     TG_LAUNCH(tg_gene_reduce_tall, tg_gene_reduce_shape(L.Kp, true), s, (const float*)b->h[i]->fp(b->h[i]->L.o_genepart), L.grb,
                               L.Kp, b->h[i]->fp(b->h[i]->L.o_genestat));
             } else TG_LAUNCH_Z(tg_gene_reduce_b, tg_gene_reduce_shape(L.Kp, false), n, s, A.gene + z0);
-            TG_LAUNCH_Z((tg_dghat_emit_b<PR>), tg_dghat_emit_shape(L.V, L.Kp, true, 1), n, s, A.emit + z0);
+            if (spatial) {      // what tg_launch_loss does with spatial terms on, launch by launch, each kernel as its twin
+                const TgShape spmm = tg_spmm_shape(L.Vs), blocks = tg_spot_blocks_shape(L.Vs), reduce = tg_stat_reduce_shape(L.Kp);
+                if (L.has_nb) {
+                    TG_LAUNCH_Z(tg_spmm_b, spmm, n, s, A.nb_spmm + z0);
+                    TG_LAUNCH_Z(tg_colstats_b, blocks, n, s, A.nb_cols + z0);
+                    TG_LAUNCH_Z(tg_gene_reduce_b, tg_gene_reduce_shape(L.Kp, false), n, s, A.nb_red + z0);
+                }
+                if (L.has_ct) {
+                    TG_LAUNCH_Z(tg_ct_mask_b, tg_ct_shape(L.Vs), n, s, A.ct_mask + z0);
+                    TG_LAUNCH_Z(tg_ct_grad_b, tg_ct_shape(L.Vs), n, s, A.ct_grad + z0);
+                }
+                TG_LAUNCH_Z(tg_loss_finalize_b, tg_loss_finalize_shape(), n, s, A.fin + z0, var, A.scr + z0);
+                if (L.has_nb) TG_LAUNCH_Z(tg_spmm_b, spmm, n, s, A.nb_grad + z0);
+                if (L.has_ac) {
+                    TG_LAUNCH_Z(tg_spmm_b, spmm, n, s, A.ac_y + z0);
+                    TG_LAUNCH_Z(tg_ac_stats1_b, blocks, n, s, A.ac + z0);
+                    TG_LAUNCH_Z(tg_stat_reduce_b, reduce, n, s, A.ac_red1 + z0);
+                    TG_LAUNCH_Z(tg_ac_stats2_b, blocks, n, s, A.ac + z0);
+                    TG_LAUNCH_Z(tg_stat_reduce_b, reduce, n, s, A.ac_red2 + z0);
+                    if (m0->cfg.lambda_geary > 0.f) TG_LAUNCH_Z(tg_spmm_b, spmm, n, s, A.ac_z + z0);
+                    TG_LAUNCH_Z(tg_ac_finalize_b, tg_ac_finalize_shape(), n, s, A.ac_fin + z0, var, A.scr + z0);
+                    TG_LAUNCH_Z(tg_ac_grad_b, blocks, n, s, A.ac + z0);
+                    TG_LAUNCH_Z(tg_stat_reduce_b, reduce, n, s, A.ac_red3 + z0);
+                    TG_LAUNCH_Z(tg_spmm_b, spmm, n, s, A.ac_gsp + z0);
+                }
+                TG_LAUNCH_Z((tg_dghat_emit_extra_b<PR>), tg_dghat_emit_shape(L.V, L.Kp, false, 1), n, s, A.emit + z0);
+            } else TG_LAUNCH_Z((tg_dghat_emit_b<PR>), tg_dghat_emit_shape(L.V, L.Kp, true, 1), n, s, A.emit + z0);
             tg_with_tile_geo(L.T, [&](auto ge) {
                 using GE = typename decltype(ge)::type;
                 TG_LAUNCH_Z((tg_bwd_kernel_b<PR, GE>), tg_bwd_shape<GE>(bt.nct, bt.nvt), n, s, A.bwd + z0);
             });
         }
-        const TgAdamStep as = tg_adam_step(m0->cfg, m0->step, lr);
-        TgStepVar var;
-        var.step_size = as.step_size; var.bc2_sqrt = as.bc2_sqrt;
-        var.hist_row = hist ? (long long)(first_row + it) : -1;
         tg_with_update_flags(L.full, x16, [&](auto fl, auto xh) {      // (a batch never streams: tg_adam_rowpass_b)
             tg_with_row_length(L.V, [&](auto nq, auto nt) {
                 constexpr int NQ = decltype(nq)::value, NT = decltype(nt)::value;
-                TG_LAUNCH_Z((tg_adam_rowpass_b<decltype(fl)::value, decltype(xh)::value, NQ, NT>), tg_adam_rowpass_shape<NT>(L.C, 1), n, s, a_up, var);
+                TG_LAUNCH_Z((tg_adam_rowpass_b<decltype(fl)::value, decltype(xh)::value, NQ, NT>), tg_adam_rowpass_shape<NT>(L.C, spatial ? 0 : 1), n, s, a_up, var);
             });
         });
         if (L.full) TG_LAUNCH_Z(tg_hist_regs_b, tg_hist_regs_shape(), n, s, A.hreg + z0, var);

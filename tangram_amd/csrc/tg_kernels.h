@@ -116,3 +116,51 @@ TG_KERNEL void TG_LAUNCH_BOUNDS(1024) tg_hist_regs_b(const TgHistRegArgs* argv, 
     a.hist += var.hist_row * TGH_NTERMS;
     tg_hist_regs_body(a);
 }
+
+// ---- the spatial terms (tg_spatial.h) and the loss kernel they need ahead of the emitter -------------------------------------------
+// A step with spatial terms runs about a dozen small dependent launches between the two GEMMs; a batch of such mappings runs each of
+// them once per group.  The solo kernels and their twins are the same bodies; the argument blocks are copied by value (see
+// tg_fwd_kernel_b).  tg_spmm is used several times per step with different operands: every use has an argument array of its own.
+struct TgColstatsArgs { const float* A; const float* B; int V, Kp; float* part; };
+struct TgStatReduceArgs { const float* part; int nparts, nstat, Kp; float* out; };
+// The history row of a batched step: row `var.hist_row` of the mapping's history, or the mapping's scratch row when no history is wanted
+TG_DEV float* tg_batch_hist_row(float* base, const TgStepVar& var, float* const* scratch_rows) {
+    return (var.hist_row >= 0 && base) ? base + var.hist_row * TGH_NTERMS : scratch_rows[blockIdx.z];
+}
+TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_spmm(TgSpmmArgs a) { tg_spmm_body(a); }
+TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_spmm_b(const TgSpmmArgs* argv) { const TgSpmmArgs a = argv[blockIdx.z]; tg_spmm_body(a); }
+TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_colstats(const float* A, const float* B, int V, int Kp, float* part) { tg_colstats_body(A, B, V, Kp, part); }
+TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_colstats_b(const TgColstatsArgs* argv) {
+    const TgColstatsArgs a = argv[blockIdx.z];
+    tg_colstats_body(a.A, a.B, a.V, a.Kp, a.part);
+}
+TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_stat_reduce(const float* part, int nparts, int nstat, int Kp, float* out) { tg_stat_reduce_body(part, nparts, nstat, Kp, out); }
+TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_stat_reduce_b(const TgStatReduceArgs* argv) {
+    const TgStatReduceArgs a = argv[blockIdx.z];
+    tg_stat_reduce_body(a.part, a.nparts, a.nstat, a.Kp, a.out);
+}
+TG_KERNEL void TG_LAUNCH_BOUNDS(64) tg_ct_mask(TgCtArgs a) { tg_ct_mask_body(a); }
+TG_KERNEL void TG_LAUNCH_BOUNDS(64) tg_ct_mask_b(const TgCtArgs* argv) { const TgCtArgs a = argv[blockIdx.z]; tg_ct_mask_body(a); }
+TG_KERNEL void TG_LAUNCH_BOUNDS(64) tg_ct_grad(TgCtArgs a) { tg_ct_grad_body(a); }
+TG_KERNEL void TG_LAUNCH_BOUNDS(64) tg_ct_grad_b(const TgCtArgs* argv) { const TgCtArgs a = argv[blockIdx.z]; tg_ct_grad_body(a); }
+TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_ac_stats1(TgAcArgs a) { tg_ac_stats1_body(a); }
+TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_ac_stats1_b(const TgAcArgs* argv) { const TgAcArgs a = argv[blockIdx.z]; tg_ac_stats1_body(a); }
+TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_ac_stats2(TgAcArgs a) { tg_ac_stats2_body(a); }
+TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_ac_stats2_b(const TgAcArgs* argv) { const TgAcArgs a = argv[blockIdx.z]; tg_ac_stats2_body(a); }
+TG_KERNEL void TG_LAUNCH_BOUNDS(1024) tg_ac_finalize(TgAcFinArgs f) { tg_ac_finalize_body(f); }
+TG_KERNEL void TG_LAUNCH_BOUNDS(1024) tg_ac_finalize_b(const TgAcFinArgs* argv, TgStepVar var, float* const* scratch_rows) {
+    TgAcFinArgs f = argv[blockIdx.z];
+    f.a.hist = tg_batch_hist_row(f.a.hist, var, scratch_rows);
+    tg_ac_finalize_body(f);
+}
+TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_ac_grad(TgAcArgs a) { tg_ac_grad_body(a); }
+TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_ac_grad_b(const TgAcArgs* argv) { const TgAcArgs a = argv[blockIdx.z]; tg_ac_grad_body(a); }
+// tg_loss_finalize (tg_stats.h) starts the history row of a step with spatial terms: same choice of the row as above
+TG_KERNEL void TG_LAUNCH_BOUNDS(1024) tg_loss_finalize_b(const TgFinalizeArgs* argv, TgStepVar var, float* const* scratch_rows) {
+    TG_LDS_DECL;
+    TgFinalizeArgs a = argv[blockIdx.z];
+    a.hist = tg_batch_hist_row(a.hist, var, scratch_rows);
+    tg_loss_scalars<true>(a, (float*)tg_lds);
+}
+// the emitter with coefficients from memory and the spatial terms' extra gradient (tg_dghat_emit<PR, true, false>)
+template <class PR> TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_dghat_emit_extra_b(const TgEmitArgs* argv) { tg_dghat_emit_body<PR, true, false>(argv[blockIdx.z]); }

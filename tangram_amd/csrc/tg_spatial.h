@@ -24,7 +24,7 @@ struct TgSpmmArgs {
 // XCD streaming the whole matrix; (ii) the non-zeros of a row are taken eight at a time with every gathered row requested before the
 // first is used (the one-at-a-time loop was a chain of ~7 dependent row loads).  Same sums in the same order: same bits.
 TG_HD TgShape tg_spmm_shape(int V) { return tg_shape(V, 1, 256, 0); }          // one workgroup per spot row
-TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_spmm(TgSpmmArgs a) {
+TG_DEV void tg_spmm_body(const TgSpmmArgs& a) {
     constexpr int U = 8;
     const int nb = gridDim.x, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
     const int q = nb >> 3, r = nb & 7;
@@ -73,7 +73,7 @@ TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_spmm(TgSpmmArgs a) {
 // the kernels over blocks of TG_RB spots: tg_colstats, tg_ac_stats1, tg_ac_stats2, tg_ac_refs, tg_ac_grad
 TG_HD TgShape tg_spot_blocks_shape(int V) { return tg_shape(tg_row_blocks(V), 1, 256, 0); }
 // per-gene partial sums over a block of TG_RB spots: (sum A*B, sum A*A)  [second stage: tg_gene_reduce]
-TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_colstats(const float* A, const float* B, int V, int Kp, float* part /*[nrb][2][Kp]*/) {
+TG_DEV void tg_colstats_body(const float* A, const float* B, int V, int Kp, float* part /*[nrb][2][Kp]*/) {
     const int rb = blockIdx.x, vbeg = rb * TG_RB;
     for (int k = threadIdx.x; k < Kp; k += 256) {
         float d = 0.f, n = 0.f;
@@ -92,7 +92,7 @@ struct TgCtArgs {
     TgCsr N; const float* Ghat; float* mask /*[Vr][Tp]*/; float* ctpart /*[V]*/; float* extra;
     int V, Kp, K, T, Tp; float lambda_ct;
 };
-TG_KERNEL void TG_LAUNCH_BOUNDS(64) tg_ct_mask(TgCtArgs a) {
+TG_DEV void tg_ct_mask_body(const TgCtArgs& a) {
     const int v = blockIdx.x, b = a.N.indptr[v], e = a.N.indptr[v + 1];
     float part = 0.f;
     for (int t = threadIdx.x; t < a.T; t += 64) {
@@ -108,7 +108,7 @@ TG_KERNEL void TG_LAUNCH_BOUNDS(64) tg_ct_mask(TgCtArgs a) {
     if (threadIdx.x == 0) a.ctpart[v] = part;
 }
 // d(penalty)/d(ct) = mask - N^T mask  -> augmentation columns of the extra gradient (a.N holds N^T here)
-TG_KERNEL void TG_LAUNCH_BOUNDS(64) tg_ct_grad(TgCtArgs a) {
+TG_DEV void tg_ct_grad_body(const TgCtArgs& a) {
     const int v = blockIdx.x, b = a.N.indptr[v], e = a.N.indptr[v + 1];
     for (int t = threadIdx.x; t < a.T; t += 64) {
         float s = 0.f;
@@ -153,7 +153,7 @@ TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_csr_rowsum(TgCsr W, int V, float* out, i
 }
 
 // stage 1: per-gene partial sums over a block of TG_RB spots
-TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_ac_stats1(TgAcArgs a) {
+TG_DEV void tg_ac_stats1_body(const TgAcArgs& a) {
     const int rb = blockIdx.x, vbeg = rb * TG_RB;
     for (int k = threadIdx.x; k < a.Kp; k += 256) {
         float s[TGAC_NSTAT];
@@ -175,7 +175,7 @@ TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_ac_stats1(TgAcArgs a) {
 }
 // deterministic second stage of any [nparts][nstat][Kp] partial array
 TG_HD TgShape tg_stat_reduce_shape(int Kp) { return tg_shape((Kp + 255) / 256, 1, 256, 0); }
-TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_stat_reduce(const float* part, int nparts, int nstat, int Kp, float* out) {
+TG_DEV void tg_stat_reduce_body(const float* part, int nparts, int nstat, int Kp, float* out) {
     const int k = blockIdx.x * 256 + threadIdx.x;
     if (k >= Kp) return;
     for (int q = 0; q < nstat; ++q) {
@@ -186,7 +186,7 @@ TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_stat_reduce(const float* part, int npart
 }
 // stage 2: with mu from stage 1: q = sum (x - mu)^2 (two-pass, no cancellation) and, for Moran,
 // h = (x - mu)(Y - mu r): partial sums of h.Tm and h^2
-TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_ac_stats2(TgAcArgs a) {
+TG_DEV void tg_ac_stats2_body(const TgAcArgs& a) {
     const int rb = blockIdx.x, vbeg = rb * TG_RB;
     for (int k = threadIdx.x; k < a.Kp; k += 256) {
         float d = 0.f, n = 0.f, qz = 0.f;
@@ -229,7 +229,8 @@ TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_ac_refs(TgAcArgs a) {
 }
 // per-gene coefficients and the three scalars (one block); stat2 = [2][Kp] (h.Tm, h^2), tnorm = [4][Kp] (rows 0 and 2: |Tg_k|^2, |Tm_k|^2)
 struct TgAcFinArgs { TgAcArgs a; const float* tnorm; };
-TG_KERNEL void TG_LAUNCH_BOUNDS(1024) tg_ac_finalize(TgAcFinArgs f) {
+TG_HD TgShape tg_ac_finalize_shape() { return tg_shape(1, 1, 1024, 64); }     // tg_ac_finalize(_b): one workgroup, one float per wave
+TG_DEV void tg_ac_finalize_body(const TgAcFinArgs& f) {
     TG_LDS_DECL;
     float* red = (float*)tg_lds;
     const TgAcArgs& a = f.a;
@@ -289,7 +290,7 @@ TG_KERNEL void TG_LAUNCH_BOUNDS(1024) tg_ac_finalize(TgAcFinArgs f) {
 }
 // gradient assembly, elementwise part: B1 = source of the W^T SpMM (Getis + Moran), D = direct part (Moran + Geary),
 // cmpart = partial sums of the Moran part's column mean (the centering Jacobian of z = x - mean(x))
-TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_ac_grad(TgAcArgs a) {
+TG_DEV void tg_ac_grad_body(const TgAcArgs& a) {
     const int rb = blockIdx.x, vbeg = rb * TG_RB;
     const float Vf = (float)a.V;
     for (int k = threadIdx.x; k < a.Kp; k += 256) {

@@ -316,6 +316,8 @@ TG_DEV void tg_loss_scalars(const TgFinalizeArgs& a, float* red) {
     }
 }
 
+// tg_loss_finalize, tg_loss_finalize_b (tg_kernels.h): one workgroup.  LDS: `red`, [16 waves][5] floats
+TG_HD TgShape tg_loss_finalize_shape() { return tg_shape(1, 1, 1024, 16 * 5 * 4); }
 TG_KERNEL void TG_LAUNCH_BOUNDS(1024) tg_loss_finalize(TgFinalizeArgs a) {
     TG_LDS_DECL;
     tg_loss_scalars<true>(a, (float*)tg_lds);

@@ -128,7 +128,7 @@ TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_adam_math_probe(const float* a, const fl
 TG_HD int tg_capped_grid(int want, int max_wg) { return (max_wg > 0 && max_wg < want) ? max_wg : want; }
 // tg_adam_update<.., NT>: one workgroup per cell row + `hist_wg` (0 / 1) that writes the deferred history row.  LDS: `red`, up to [NT / 64][5] floats
 template <int NT> TG_HD TgShape tg_adam_update_shape(int rows, int hist_wg) { return tg_shape(rows + hist_wg, 1, NT, NT == 1024 ? 512 : 128); }
-// tg_adam_rowpass(_b)<.., NT, ..>: likewise (a batch always launches the history workgroup).  LDS: `red` + `red2`, [NT / 64][TGP1_N + 2] floats at most
+// tg_adam_rowpass(_b)<.., NT, ..>: likewise (a batch launches the history workgroup unless its mappings carry spatial terms: fin_on = 0, hist_wg = 0).  LDS: `red` + `red2`, [NT / 64][TGP1_N + 2] floats at most
 template <int NT> TG_HD TgShape tg_adam_rowpass_shape(int rows, int hist_wg) { return tg_shape(rows + hist_wg, 1, NT, 256); }
 // NT = 256 threads per cell; 1 024 for a handful of long rows (clusters mode beyond 16 384 spots: with 18 workgroups the kernel is
 // one dependent chain of V / (4 NT) trips per thread -- 81 us at 50 000 spots with 256 threads)
