@@ -235,6 +235,26 @@ int tg_mapper_result_topk(tg_mapper* m, int32_t k, float* val_out_dev /*[C][k]*/
 int tg_topk_merge(const float* val_in_dev, const int32_t* idx_in_dev, int64_t n_rows, int32_t n_in, int64_t ld_in,
                   int32_t k, float* val_out_dev, int32_t* idx_out_dev, void* hip_stream);
 
+/* Each SPOT's k most probable cells WITHOUT the dense mapping -- the column reading of the same matrix (which cells sit in a spot:
+ * deconvolution, per-spot cell lists), which the row-wise lists above cannot give: a spot's strongest cell need not have that spot
+ * among its own k best.  One streaming pass over the logits, each read once.  val_out_dev [V][k]: the k largest entries of column v
+ * of softmax(M) over this handle's V spots -- the very bits tg_mapper_result writes --, cell_out_dev [V][k]: their cell indices.
+ * Order: value descending, equal values by ascending cell index, decided on the computed probabilities, not on the logits.
+ * 1 <= k <= 32 (TG_SPOT_TOPK_MAX), else TG_ERR_INVALID; k may exceed the number of cells: a spot with fewer admitted cells than k
+ * ends in (0.0f, -1).  min_filter (constrained mode): a cell takes part only if its filter value f_c -- what tg_mapper_result
+ * returns as F_out -- is > min_filter (the reference's `F_out > threshold`, utils.py count_cell_annotations /
+ * project_cell_annotations); a negative value or NaN admits every cell; a non-negative one on an unconstrained handle is
+ * TG_ERR_INVALID.  colsum_out_dev [V] or NULL: sum_c p[c][v] over the admitted cells, accumulated in fp64 in a fixed order (cells
+ * ascending inside a slab, slabs ascending) and rounded once to fp32; NULL: no fp64 work is done.
+ * The cells are cut into slabs of slab_rows rows whose lists are merged by one further launch; slab_rows = 0: the library chooses
+ * (about 1 000 workgroups, slabs of at least 256 rows); a positive value (>= 8) forces the height.  The lists and values do not
+ * depend on it.  scratch_dev: 8-byte aligned, tg_mapper_spot_topk_query_bytes(m, k, slab_rows) bytes, never NULL.
+ * A spot shard owns whole columns and every cell: its answer is final for its spots.  Asynchronous on the handle's stream; no
+ * atomics; allocates nothing and writes nothing but the outputs and the scratch: training continues bit for bit afterwards.      */
+int tg_mapper_spot_topk_query_bytes(const tg_mapper* m, int32_t k, int32_t slab_rows, size_t* bytes_out);
+int tg_mapper_result_spot_topk(tg_mapper* m, int32_t k, float min_filter, int32_t slab_rows, void* scratch_dev,
+                               float* val_out_dev /*[V][k]*/, int32_t* cell_out_dev /*[V][k]*/, float* colsum_out_dev /*[V] or NULL*/);
+
 /* Replaces `adata_map.X.T @ S` (mapping_utils.py:402): Ghat_out_dev [V][K] = softmax(M)^T S (times f). */
 int tg_mapper_project(tg_mapper* m, float* Ghat_out_dev);
 

@@ -19,7 +19,10 @@ PRECISIONS = {"fp32": 0, "bf16": 1, "bf16x3": 2}
 H_NTERMS = 16
 TOPK_MAX = 64          # TG_TOPK_MAX / TG_TOPK_CHUNK of csrc/tg_topk.h (checked against tg_debug_topk_limits by the tests)
 TOPK_CHUNK = 8192
-CONSIST_MAX_RUNS = 8   # TG_CONSIST_MAX_RUNS of csrc/tg_consist.h
+SPOT_TOPK_MAX = 32     # TG_SPOT_TOPK_MAX of csrc/tg_spot_topk.h: the largest k of result_spot_topk (these three are checked against
+SPOT_TOPK_STRIP = 256  # TG_SPOT_STRIP: spots per workgroup                                          tg_debug_spot_topk_limits by the tests)
+SPOT_TOPK_MIN_SLAB_ROWS = 8   # TG_SPOT_UNROLL: rows loaded ahead = the smallest slab_rows a caller may force
+CONSIST_MAX_RUNS = 8  # TG_CONSIST_MAX_RUNS of csrc/tg_consist.h
 H_TOTAL, H_MAIN, H_VG, H_KL, H_ENTROPY, H_L1, H_L2, H_NB, H_CT, H_COUNT, H_FREG, H_GETIS, H_MORAN, H_GEARY = range(14)
 
 
@@ -82,6 +85,9 @@ def _signatures():
         "tg_mapper_result": (i32, [vp, vp, vp]),
         "tg_mapper_result_topk": (i32, [vp, i32, vp, vp]),
         "tg_topk_merge": (i32, [vp, vp, i64, i32, i64, i32, vp, vp, vp]),
+        "tg_mapper_spot_topk_query_bytes": (i32, [vp, i32, i32, P(sz)]),
+        "tg_mapper_result_spot_topk": (i32, [vp, i32, f32, i32, vp, vp, vp, vp]),
+        "tg_debug_spot_topk_limits": (i32, [i32, i32, P(i32)]),
         "tg_mapper_project": (i32, [vp, vp]),
         "tg_mapper_project_genes": (i32, [vp, vp, i64, i32, vp, i64, i32]),
         "tg_csr_columns_to_dense": (i32, [vp, vp, vp, i64, i32, i32, vp, i64, vp]),

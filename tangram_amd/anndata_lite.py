@@ -1,4 +1,4 @@
-"""A minimal AnnData-shaped container (X, obs, var, uns, obsm, obsp + `adata[:, genes]`), used
+"""A minimal AnnData-shaped container (X, obs, var, uns, obsm, obsp, varm + `adata[:, genes]`), used
 (a) as the return type of `map_cells_to_space` when the `anndata` package is not installed and
 (b) as the stand-in input in tests (the authoring/GPU images have neither scanpy nor anndata).
 It implements only what tangram/mapping_utils.py:141-428 touches."""
@@ -9,7 +9,7 @@ import pandas as pd
 
 
 class AnnDataLite:
-    def __init__(self, X, obs=None, var=None, uns=None, obsm=None, obsp=None):
+    def __init__(self, X, obs=None, var=None, uns=None, obsm=None, obsp=None, varm=None):
         self.X = X
         n_obs, n_var = X.shape
         self.obs = obs if obs is not None else pd.DataFrame(index=[str(i) for i in range(n_obs)])
@@ -19,6 +19,7 @@ class AnnDataLite:
         self.uns = uns if uns is not None else {}
         self.obsm = obsm if obsm is not None else {}
         self.obsp = obsp if obsp is not None else {}
+        self.varm = varm if varm is not None else {}                 # per-variable arrays [n_var, ...]
 
     @property
     def n_obs(self):
@@ -53,10 +54,11 @@ class AnnDataLite:
             if (idx < 0).any():
                 raise KeyError("unknown variable names")
         X = self.X[:, idx]
-        return AnnDataLite(X, obs=self.obs, var=self.var.iloc[idx].copy(), uns=self.uns, obsm=self.obsm, obsp=self.obsp)
+        return AnnDataLite(X, obs=self.obs, var=self.var.iloc[idx].copy(), uns=self.uns, obsm=self.obsm, obsp=self.obsp,
+                           varm={k: np.asarray(v)[idx] for k, v in self.varm.items()})
 
     def copy(self):
-        return AnnDataLite(self.X.copy(), self.obs.copy(), self.var.copy(), dict(self.uns), dict(self.obsm), dict(self.obsp))
+        return AnnDataLite(self.X.copy(), self.obs.copy(), self.var.copy(), dict(self.uns), dict(self.obsm), dict(self.obsp), dict(self.varm))
 
 
 def make_result_anndata(X, obs, var):

@@ -2143,6 +2143,78 @@ extern "C" int tg_topk_merge(const float* val_in_dev, const int32_t* idx_in_dev,
     return TG_OK;
 }
 
+// ---- each spot's k most probable cells (tg_spot_topk.h) -----------------------------------------
+// The plan of one call: slab height, slabs, and the caller's scratch -- [V][slabs * k] floats, [V][slabs * k] int32 (the slabs' lists;
+// not used with one slab, whose list IS the result), then [slabs][V] doubles (the slabs' column sums), 8-byte aligned.
+struct TgSpotPlan { int rows, n_slabs; size_t o_cell, o_col, bytes; };
+static int tg_spot_topk_plan(const tg_mapper* m, int32_t k, int32_t slab_rows, TgSpotPlan* p) {
+    if (!m || !m->ready) return tg_fail(TG_ERR_STATE, "mapper not ready");
+    if (k < 1 || k > TG_SPOT_TOPK_MAX) return tg_fail(TG_ERR_INVALID, "spot top-k: k = %d is outside [1, %d]", k, TG_SPOT_TOPK_MAX);
+    if (slab_rows < 0 || (slab_rows > 0 && slab_rows < TG_SPOT_UNROLL))
+        return tg_fail(TG_ERR_INVALID, "spot top-k: slab_rows = %d: 0 (the library chooses) or at least %d", slab_rows, TG_SPOT_UNROLL);
+    const TgLayout& L = m->L;
+    p->rows = tg_spot_topk_slab_rows(L.C, L.V, slab_rows);
+    const long long n_slabs = ((long long)L.C + p->rows - 1) / p->rows;
+    if (n_slabs > TG_SPOT_MAX_SLABS || n_slabs * k > 0x7fffffffLL)
+        return tg_fail(TG_ERR_INVALID, "spot top-k: slab_rows = %d cuts %d cells into %lld slabs, more than %d", slab_rows, L.C, n_slabs, TG_SPOT_MAX_SLABS);
+    p->n_slabs = (int)n_slabs;
+    const size_t lists = n_slabs > 1 ? rup((size_t)L.V * (size_t)n_slabs * (size_t)k * 4, 8) : 0;
+    p->o_cell = lists; p->o_col = 2 * lists;
+    p->bytes = p->o_col + (size_t)n_slabs * (size_t)L.V * 8;
+    return TG_OK;
+}
+
+extern "C" int tg_mapper_spot_topk_query_bytes(const tg_mapper* m, int32_t k, int32_t slab_rows, size_t* bytes_out) {
+    if (!bytes_out) return tg_fail(TG_ERR_INVALID, "spot top-k: bytes_out is NULL");
+    TgSpotPlan p;
+    const int rc = tg_spot_topk_plan(m, k, slab_rows, &p);
+    if (rc) return rc;
+    *bytes_out = p.bytes;
+    return TG_OK;
+}
+
+template <int KL> static void tg_launch_spot_topk(tg_mapper* m, const TgSpotTopkArgs& a, int n_slabs, bool sum) {
+    if (sum) TG_LAUNCH((tg_spot_topk<KL, true>), tg_spot_topk_shape(a.V, n_slabs), m->stream, a);
+    else TG_LAUNCH((tg_spot_topk<KL, false>), tg_spot_topk_shape(a.V, n_slabs), m->stream, a);
+}
+
+extern "C" int tg_mapper_result_spot_topk(tg_mapper* m, int32_t k, float min_filter, int32_t slab_rows, void* scratch_dev,
+                                          float* val_out_dev, int32_t* cell_out_dev, float* colsum_out_dev) {
+    TgSpotPlan p;
+    const int rc = tg_spot_topk_plan(m, k, slab_rows, &p);
+    if (rc) return rc;
+    if (!val_out_dev || !cell_out_dev) return tg_fail(TG_ERR_INVALID, "spot top-k: an output is NULL");
+    if (!scratch_dev) return tg_fail(TG_ERR_INVALID, "spot top-k: scratch is NULL");
+    const bool filtered = min_filter >= 0.f;                              // (false for NaN)
+    if (filtered && m->cfg.mode != TG_MODE_CONSTRAINED)
+        return tg_fail(TG_ERR_INVALID, "spot top-k: min_filter = %g given to an unconstrained mapper, which has no filter (pass a negative value)", (double)min_filter);
+    const TgLayout& L = m->L;
+    unsigned char* scratch = (unsigned char*)scratch_dev;
+    const bool direct = p.n_slabs == 1;
+    TgSpotTopkArgs a;
+    a.M = (const float*)(m->st + L.s_M); a.rshift = m->fp(L.o_rshift); a.rinvz = m->fp(L.o_rinvz);
+    a.gate = filtered ? m->fp(L.o_fgate) : nullptr; a.min_filter = min_filter;
+    a.C = L.C; a.V = L.V; a.Vp = L.Vp; a.k = k; a.slab_rows = p.rows;
+    a.ld = (long long)p.n_slabs * k;
+    a.val = direct ? val_out_dev : (float*)scratch;
+    a.cell = direct ? (int*)cell_out_dev : (int*)(scratch + p.o_cell);
+    a.colpart = (double*)(scratch + p.o_col);
+    const bool sum = colsum_out_dev != nullptr;
+    switch (tg_spot_topk_list_len(k)) {
+        case 1: tg_launch_spot_topk<1>(m, a, p.n_slabs, sum); break;
+        case 4: tg_launch_spot_topk<4>(m, a, p.n_slabs, sum); break;
+        case 8: tg_launch_spot_topk<8>(m, a, p.n_slabs, sum); break;
+        case 16: tg_launch_spot_topk<16>(m, a, p.n_slabs, sum); break;
+        default: tg_launch_spot_topk<32>(m, a, p.n_slabs, sum); break;
+    }
+    if (!direct)
+        TG_LAUNCH(tg_topk_merge_rows, tg_spot_merge_shape(L.V), m->stream, (const float*)a.val, (const int*)a.cell, (int)a.ld, a.ld, (int)k,
+                  val_out_dev, (int*)cell_out_dev);
+    if (sum) TG_LAUNCH(tg_spot_colsum_finish, tg_spot_colsum_finish_shape(L.V), m->stream, (const double*)a.colpart, p.n_slabs, L.V, colsum_out_dev);
+    TG_LAUNCH_CK();
+    return TG_OK;
+}
+
 extern "C" int tg_mapper_project(tg_mapper* m, float* Ghat_out_dev) {
     if (!m || !m->ready) return tg_fail(TG_ERR_STATE, "mapper not ready");
     if (!Ghat_out_dev) return tg_fail(TG_ERR_INVALID, "Ghat_out is NULL");
@@ -2821,6 +2893,12 @@ extern "C" int tg_debug_fwd_cover(const tg_config* cfg, long long* out) {
 // the compile-time limits of tg_topk.h: out[0] = largest k, out[1] = spots per chunk of tg_row_topk
 extern "C" int tg_debug_topk_limits(int32_t out[2]) {
     out[0] = TG_TOPK_MAX; out[1] = TG_TOPK_CHUNK;
+    return TG_OK;
+}
+// the compile-time limits of tg_spot_topk.h: out[0] = largest k, out[1] = spots per strip, out[2] = rows loaded ahead (the smallest
+// slab_rows), out[3] = the slab height the library would choose for n_cells x n_spots
+extern "C" int tg_debug_spot_topk_limits(int32_t n_cells, int32_t n_spots, int32_t out[4]) {
+    out[0] = TG_SPOT_TOPK_MAX; out[1] = TG_SPOT_STRIP; out[2] = TG_SPOT_UNROLL; out[3] = tg_spot_topk_slab_rows(n_cells, n_spots, 0);
     return TG_OK;
 }
 // where the spot-major image lies in a tg_sparse_map_build workspace: out[0..2] = byte offsets of spot_ptr (int64 [n_spots + 1]),

@@ -22,7 +22,8 @@
 //   (MapperConstrained), tg_merge_stats, tg_spmm / tg_ct_* / tg_ac_* (spatial terms), tg_row_entropy / tg_val_finalize,
 //   tg_row_topk / tg_topk_merge_rows (each cell's k most probable spots without the dense mapping, tg_topk.h),
 //   tg_sp_count / _scan / _scatter / _order + tg_sp_project (genes projected from a sparse mapping, tg_sparse.h),
-//   tg_consist_rows / tg_consist_finish (agreement of repeated mappings from their logits, tg_consist.h).
+//   tg_consist_rows / tg_consist_finish (agreement of repeated mappings from their logits, tg_consist.h),
+//   tg_spot_topk / tg_spot_colsum_finish (each spot's k most probable cells without the dense mapping, tg_spot_topk.h).
 //
 // Data layout in HBM: M, Adam m, Adam v are C x Vp fp32 row-major (Vp = V rounded up to 64);
 // S is kept twice in operand format: St [Kp][Cp] (cell index contiguous, for the forward contraction
@@ -68,6 +69,7 @@ struct TgStepVar { float step_size, bc2_sqrt; long long hist_row; };    // hist_
 #include "tg_topk.h"
 #include "tg_sparse.h"
 #include "tg_consist.h"
+#include "tg_spot_topk.h"
 
 // ----------------------------------------------------------------------------------------------
 // Kernel entry points of the iteration.  Every kernel of the single-GPU Mapper step exists twice: with its arguments by value

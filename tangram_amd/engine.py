@@ -252,6 +252,26 @@ class HipMapperEngine:
                    out_i.data_ptr(), self._hip_stream, tensors=(val, idx, out_v, out_i))
         return out_v, out_i
 
+    def result_spot_topk(self, k, min_filter=None, colsum=False, slab_rows=0):
+        """Each spot's k most probable cells of this handle's spots -- the column reading of the mapping: (values [V, k] float32,
+        cells [V, k] int32[, column sums [V] float32]) device tensors, value descending, equal values by ascending cell; the values
+        are the bits `result()` holds at those places; 1 <= k <= 32 (_capi.SPOT_TOPK_MAX); a spot with fewer admitted cells than k
+        ends in (0, -1).  One pass over the logits (tg_mapper_result_spot_topk): no C x V plane is written.  `min_filter`
+        (constrained mode only): only cells whose filter value is > min_filter take part; None admits every cell.  `colsum=True`:
+        also each spot's sum over the admitted cells (fp64 accumulation, rounded once).  `slab_rows`: 0 = the library cuts the cells
+        into slabs; a value >= 8 forces the slab height (the lists do not depend on it)."""
+        k, slab_rows = int(k), int(slab_rows)
+        thr = -1.0 if min_filter is None else float(min_filter)
+        nbytes = ct.c_size_t()
+        self._call(self._lib.tg_mapper_spot_topk_query_bytes, self._h, k, slab_rows, ct.byref(nbytes))
+        scratch = torch.empty((max(nbytes.value, 8) + 7) // 8, dtype=torch.int64, device=self.device)
+        val = torch.empty((self.V, k), dtype=torch.float32, device=self.device)
+        cell = torch.empty((self.V, k), dtype=torch.int32, device=self.device)
+        total = torch.empty((self.V,), dtype=torch.float32, device=self.device) if colsum else None
+        self._call(self._lib.tg_mapper_result_spot_topk, self._h, k, thr, slab_rows, scratch.data_ptr(), val.data_ptr(), cell.data_ptr(),
+                   total.data_ptr() if colsum else None, tensors=(scratch, val, cell, total))
+        return (val, cell, total) if colsum else (val, cell)
+
     def project(self):
         Gh = torch.empty((self.V, self.K), dtype=torch.float32, device=self.device)
         self._call(self._lib.tg_mapper_project, self._h, Gh.data_ptr(), tensors=(Gh,))

@@ -124,6 +124,25 @@ def _result_topk(mapper, k):
     return val.detach().cpu().numpy(), idx.detach().cpu().numpy()
 
 
+def _result_spot_topk(mapper, k, threshold=None, mass=False):
+    """NumPy (values [V, k], cells [V, k][, mass [V]]) of a trained mapper over ALL its spots; a sharded mapper gathers its ranks'
+    blocks (collective).  mass = (sum of the k values) / (the spot's column sum over the admitted cells), formed in float64 from
+    the float32 lists and column sums; NaN for a spot that no cell is admitted to."""
+    got = (mapper._sharded or mapper._engine).result_spot_topk(k, min_filter=threshold, colsum=bool(mass))
+    val, cell = got[0].detach().cpu().numpy(), got[1].detach().cpu().numpy()
+    if not mass:
+        return val, cell
+    total = got[2].detach().cpu().numpy().astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        share = val.astype(np.float64).sum(axis=1) / total
+    return val, cell, share.astype(np.float32)
+
+
+def _spot_top_dict(mapper, k, threshold=None):
+    val, cell, share = _result_spot_topk(mapper, k, threshold, mass=True)
+    return {"spot_top_cells": cell, "spot_top_values": val, "spot_top_k_mass": share, "spot_top_k": int(k)}
+
+
 def _n_spots_total(mapper):
     return int(mapper._sharded.n_spots_total) if mapper._sharded is not None else int(mapper._engine.V)
 
@@ -189,6 +208,7 @@ class Mapper:
             raise ValueError("init must be 'reference' (NumPy's stream, like the reference) or 'device'")
         self._gather_result = bool(gather_result)
         self.spot_range = None
+        self.spot_top = None                                 # train(spot_top_k=k): each spot's k most probable cells
         lambda_getis_ord = lambda_getis_ord if (lambda_getis_ord and lambda_getis_ord > 0) else 0.0     # reference :170,:174,:179
         lambda_moran = lambda_moran if (lambda_moran and lambda_moran > 0) else 0.0
         lambda_geary = lambda_geary if (lambda_geary and lambda_geary > 0) else 0.0
@@ -272,11 +292,24 @@ class Mapper:
         On a sharded run: collective, every rank gets the same global result."""
         return _result_topk(self, k)
 
-    def train(self, num_epochs, learning_rate=0.1, print_each=100, val_each=None, *, top_k=None):
+    def result_spot_topk(self, k, *, mass=False):
+        """Each SPOT's k most probable cells of the current mapping -- which cells sit in a spot: NumPy (values [V, k] float32,
+        cells [V, k] int32), value descending, equal values by ascending cell; 1 <= k <= 32; a k beyond the number of cells ends
+        every list in (0, -1).  The values are the entries of the mapping matrix at those places; the dense C x V matrix is never
+        formed (one pass over the logits on the device, V x k pairs come to the host).  `result_topk` cannot answer this: a spot's
+        strongest cell need not have that spot among its own k best.  mass=True adds [V] float32: the share of each spot's column
+        sum that its k cells hold.  On a sharded run: collective, every rank gets the same global result.
+        Out of scope: `MapperBatch` handles (call this on a member mapper) and any annotation roll-up built on the lists."""
+        return _result_spot_topk(self, k, None, mass)
+
+    def train(self, num_epochs, learning_rate=0.1, print_each=100, val_each=None, *, top_k=None, spot_top_k=None):
         """Run the optimizer; returns (mapping matrix ndarray [C, V], training_history) like the reference (:358-408).
         top_k=k (1 .. 64): the mapping comes back as a canonical scipy.sparse.csr_matrix [C, V_total] that holds each cell's k
         largest entries (`result_topk`) -- the dense matrix is neither written on the device nor copied to the host; `gather_result`
-        is ignored."""
+        is ignored.
+        spot_top_k=k (1 .. 32; independent of top_k): after the last epoch `self.spot_top` holds each spot's k most probable cells
+        (`result_spot_topk(k, mass=True)`) as {"spot_top_cells" [V, k], "spot_top_values" [V, k], "spot_top_k_mass" [V],
+        "spot_top_k": k} -- what map_cells_to_space puts on its adata_map; what is returned does not change."""
         if self.random_state:
             torch.manual_seed(seed=self.random_state)        # reference :371-372 (no RNG is consumed afterwards)
         if print_each:
@@ -303,6 +336,8 @@ class Mapper:
                 _print_terms([(name, float(row[col])) for name, col in _PRINT_NAMES])
             if val_each is not None and (t - 1) % val_each == 0:
                 val_rows.append((self._sharded or eng).validate())   # reference :398-403: after optimizer.step() of epoch t-1
+        if spot_top_k is not None:
+            self.spot_top = _spot_top_dict(self, spot_top_k)
         if top_k is not None:
             output = _topk_csr(*_result_topk(self, top_k), _n_spots_total(self))
         elif self._sharded is not None and not self._gather_result:
@@ -373,6 +408,7 @@ class MapperConstrained:
             raise ValueError("init must be 'reference' (NumPy's stream, like the reference) or 'device'")
         self._gather_result = bool(gather_result)
         self.spot_range = None
+        self.spot_top = None                                 # train(spot_top_k=k): each spot's k most probable cells
         self.device = torch.device(device)
         self.random_state = random_state
         S = _to_numpy_f32(S)
@@ -420,10 +456,17 @@ class MapperConstrained:
         """Like Mapper.result_topk, of softmax(M) WITHOUT the filter -- what `adata_map.X` holds (:637)."""
         return _result_topk(self, k)
 
-    def train(self, num_epochs, learning_rate=0.1, print_each=100, *, top_k=None):
+    def result_spot_topk(self, k, threshold=None, *, mass=False):
+        """Like Mapper.result_spot_topk, of softmax(M) WITHOUT the filter factor -- the entries of `adata_map.X` (:637).
+        `threshold`: only cells whose filter value is > threshold take part (the reference's `F_out > threshold`); None: every
+        cell.  With a threshold, lists, pads and mass refer to the admitted cells alone; the mass of a spot without any is NaN."""
+        return _result_spot_topk(self, k, threshold, mass)
+
+    def train(self, num_epochs, learning_rate=0.1, print_each=100, *, top_k=None, spot_top_k=None):
         """Returns (mapping matrix [C, V], filter [C], training_history) like the reference (:589-639).
         History values are strings like the reference's (`str(x)`, :630); `total_loss` is `str(float)` rather than
-        the reference's tensor repr.  top_k: as for `Mapper.train` (the filter comes back whole)."""
+        the reference's tensor repr.  top_k, spot_top_k: as for `Mapper.train` (the filter comes back whole; the spot lists are
+        taken without a threshold)."""
         if self.random_state:
             torch.manual_seed(seed=self.random_state)
         eng = self._engine
@@ -443,6 +486,8 @@ class MapperConstrained:
                     self._sharded.checked()
                 row = hist[t - 1].detach().cpu().numpy()
                 _print_terms([(name, float(row[col])) for name, col in _PRINT_NAMES_CONSTRAINED])
+        if spot_top_k is not None:
+            self.spot_top = _spot_top_dict(self, spot_top_k)
         if top_k is not None:
             P = _topk_csr(*_result_topk(self, top_k), _n_spots_total(self))
             return P, eng.filter_values().detach().cpu().numpy(), self._history_dict(hist[:num_epochs])

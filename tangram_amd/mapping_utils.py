@@ -157,6 +157,7 @@ def map_cells_to_space(
     s_exact="auto",
     init="reference",
     top_k=None,
+    spot_top_k=None,
 ):
     """Map single cell data (`adata_sc`) on spatial data (`adata_sp`); see the reference docstring (:169-203).
 
@@ -172,7 +173,12 @@ def map_cells_to_space(
     `top_k=k` (opt-in, 1 .. 64): `adata_map.X` is a scipy CSR matrix with each cell's k most probable spots instead of the dense
     cells x spots array (never written, never copied to the host), `adata_map.obs["top_k_mass"]` the share of each cell's mapping
     those k entries hold, `adata_map.uns["top_k"] = k`; the training scores and the history are those of the dense call.
-    `project_genes` on such a result needs `mapper=` (keep_mapper=True)."""
+    `project_genes` on such a result needs `mapper=` (keep_mapper=True).
+    `spot_top_k=k` (opt-in, 1 .. 32, independent of `top_k`): each SPOT's k most probable cells, taken on the device from the
+    resident logits (Mapper.result_spot_topk): `adata_map.varm["spot_top_cells"]` [n_spots, k] int32 (positions in `adata_map.obs`;
+    -1 behind the last cell when k exceeds their number), `adata_map.varm["spot_top_values"]` [n_spots, k] float32 (the entries of
+    X at those places, descending), `adata_map.var["spot_top_k_mass"]` the share of each spot's column sum those k cells hold,
+    `adata_map.uns["spot_top_k"] = k`.  Constrained mode: no threshold on the filter (MapperConstrained.result_spot_topk takes one)."""
     # ---- argument checks, reference :205-229
     if lambda_g1 == 0:
         raise ValueError("lambda_g1 cannot be 0.")
@@ -239,6 +245,8 @@ def map_cells_to_space(
     device = torch.device(device)                                             # :310
     print_each = 100 if verbose else None                                     # :312-315
     topk_kw = {} if top_k is None else {"top_k": int(top_k)}
+    if spot_top_k is not None:
+        topk_kw["spot_top_k"] = int(spot_top_k)
 
     if mode in ["cells", "clusters"]:
         voxel_weights, neighborhood_filter, ct_encode, spatial_weights = None, None, None, None      # :318-329
@@ -287,6 +295,11 @@ def map_cells_to_space(
     if top_k is not None:
         adata_map.obs["top_k_mass"] = np.asarray(mapping_matrix.astype(np.float64).sum(axis=1)).reshape(-1)
         adata_map.uns["top_k"] = int(top_k)
+    if spot_top_k is not None:
+        adata_map.varm["spot_top_cells"] = mapper.spot_top["spot_top_cells"]
+        adata_map.varm["spot_top_values"] = mapper.spot_top["spot_top_values"]
+        adata_map.var["spot_top_k_mass"] = mapper.spot_top["spot_top_k_mass"]
+        adata_map.uns["spot_top_k"] = int(spot_top_k)
 
     # ---- per-gene training score, :401-410 (projection evaluated on the GPU; constrained: unfiltered like :402)
     if mode == "constrained":

@@ -413,6 +413,24 @@ class ShardedMapperEngine:
         C = val.shape[0]
         return self.eng.topk_merge(both[0].reshape(C, self.world * k).view(torch.float32), both[1].reshape(C, self.world * k), k)
 
+    def result_spot_topk(self, k, min_filter=None, colsum=False, slab_rows=0):
+        """Each spot's k most probable cells over ALL spots (collective): (values [V_total, k] float32, cells [V_total, k] int32
+        [, column sums [V_total] float32]) device tensors in global spot order, identical on every rank.  A shard owns whole columns
+        and every cell, so its local lists (HipMapperEngine.result_spot_topk) are final for its spots: they are gathered once in rank
+        order (blocks of unequal width travel padded to the widest; values and sums bit-cast to int32 beside the cells) -- no merge."""
+        k = int(k)
+        self.peer_check()
+        got = self.eng.result_spot_topk(k, min_filter=min_filter, colsum=colsum, slab_rows=slab_rows)
+        widths = [b - a for a, b in (shard_bounds(self.n_spots_total, self.world, r, self.spatial) for r in range(self.world))]
+        cols = [got[0].view(torch.int32), got[1]] + ([got[2].view(torch.int32).unsqueeze(1)] if colsum else [])
+        mine = torch.zeros((max(widths), 2 * k + (1 if colsum else 0)), dtype=torch.int32, device=got[0].device)
+        mine[:got[0].shape[0]] = torch.cat(cols, dim=1)
+        outs = [torch.empty_like(mine) for _ in range(self.world)]
+        self.pycomm.all_gather(outs, mine)
+        both = torch.cat([o[:w] for o, w in zip(outs, widths)], dim=0)                  # [V_total, 2 k (+ 1)]
+        val, cell = both[:, :k].contiguous().view(torch.float32), both[:, k:2 * k].contiguous()
+        return (val, cell, both[:, 2 * k].contiguous().view(torch.float32)) if colsum else (val, cell)
+
     def _gather_columns_host(self, X_local):
         bounds = [shard_bounds(self.n_spots_total, self.world, r, self.spatial) for r in range(self.world)]
         if not hasattr(self.pycomm, "broadcast"):
