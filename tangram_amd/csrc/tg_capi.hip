@@ -2247,8 +2247,8 @@ extern "C" int tg_mapper_project_genes(tg_mapper* m, const float* S_dev, int64_t
     // adata_map.X is softmax(M) without the filter (mapping_optimizer.py:637): row constants 1/Z and (max + ln Z) log2(e)
     const bool plain = unfiltered && m->cfg.mode == TG_MODE_CONSTRAINED;
     if (plain)
-        TG_LAUNCH(tg_plain_rscale, tg_shape((L.C + 255) / 256, 1, 256, 0), m->stream, (const float*)m->fp(L.o_rshift),
-                  (const float*)m->fp(L.o_rinvz), L.C, m->fp(L.o_rowent));
+        TG_LAUNCH(tg_plain_rscale, tg_shape((L.Cp + 255) / 256, 1, 256, 0), m->stream, (const float*)m->fp(L.o_rshift),
+                  (const float*)m->fp(L.o_rinvz), L.C, L.Cp, m->fp(L.o_rowent));
     for (int k0 = 0; k0 < n_genes; k0 += L.K) {
         const int kc = (n_genes - k0 < L.K) ? n_genes - k0 : L.K;
         int rc = tg_with_precision(tg_project_genes_precision(m->cfg.precision), [&](auto pr) {

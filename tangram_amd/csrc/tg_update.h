@@ -641,10 +641,13 @@ TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_merge_stats(TgMergeArgs a) { tg_merge_st
 TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_merge_stats_b(const TgMergeArgs* argv) { tg_merge_stats_body<false>(argv[blockIdx.z]); }
 TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_merge_stats_x(TgMergeArgs a, TgPeerLink link) { tg_merge_stats_body<true>(a, &link); }
 
-// forward row constant of the bf16 path WITHOUT the constrained-mode filter: (max + ln Z) * log2(e)
-TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_plain_rscale(const float* rshift, const float* rinvz, int C, float* out) {
+// forward row constant of the bf16 path WITHOUT the constrained-mode filter: (max + ln Z) * log2(e); one thread per row of out[Cp].
+// The padding rows C .. Cp take +3e38 like those of o_rscale (=> P = 0): the forward stages them from the LAST cell's logits, and
+// with a constant of 0 a logit above 88.7 gives P = +inf, which times the zero cell of the S^T image is NaN.
+TG_KERNEL void TG_LAUNCH_BOUNDS(256) tg_plain_rscale(const float* rshift, const float* rinvz, int C, int Cp, float* out) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c < C) out[c] = (rshift[c] - tg_log(rinvz[c])) * TG_LOG2E;
+    else if (c < Cp) out[c] = 3.0e38f;
 }
 
 // one block per row: (max, sum exp) of a row of M (initialisation / fallback path)
